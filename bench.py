@@ -17,8 +17,13 @@ hand3d_amd/dist.py (the launcher above only starts the processes and exports RAN
 imported in exactly one place, the `cpu_baseline` leg, where torch-CPU (oneDNN) convolutions ARE the baseline.
 
 Protocol: W untimed warm-up steps; barrier + device sync; EXACTLY K steps timed with per-launch profiling OFF; device sync
-+ barrier; max over ranks -> `value`.  Then a SEPARATE pass of K steps with HIP events around every launch (on the engine
-stream) gives the per-kernel durations behind `roofline` (reported with its own ms/step so the two can be compared).
++ barrier; max over ranks -> `value` and `ms_per_step`.  That is all a plain run does before it prints its line
+(`--dump-outputs DIR` also writes what the last timed step computed).
+
+`--full` adds everything else, as separate measurements after the headline region: two more K-step regions (`value` is
+then the median of three, `value_min` / `value_max` the other two), a SEPARATE pass of K steps with HIP events around every
+launch (on the engine stream) that gives the per-kernel durations behind `roofline` (reported with its own ms/step so the two
+can be compared; `--layers` runs this pass too), `host_path`, `other_configs` and the `cpu_baseline` / `epe_vs_oracle` leg.
 """
 import argparse
 import json
@@ -45,16 +50,22 @@ def parse():
     ap.add_argument('--height', type=int, default=320)
     ap.add_argument('--width', type=int, default=320)
     ap.add_argument('--workload', default='full', choices=['full', 'posenet'])
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: three timed regions, the profiled roofline pass, host_path, other_configs and the '
+                         'cpu_baseline / epe_vs_oracle leg (a plain run only sets up, warms up, times K steps and prints its line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB in all)')
     ap.add_argument('--cpu-seconds', type=float, default=20.0,
-                    help='budget of the cpu_baseline / epe_vs_oracle leg on rank 0 at N=1 (0 = skip)')
+                    help='budget of the cpu_baseline / epe_vs_oracle leg on rank 0 at N=1 (with --full; 0 = skip)')
     ap.add_argument('--layers', action='store_true', help='print the per-layer table to stderr')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f16'],
                     help="f32 = exact f32 MFMA (headline); f16 = half-precision trunks, BASELINE config 5 (looser parity)")
     ap.add_argument('--graph', action='store_true', help='replay each step as one hipGraph (hp3d_set_option graph=1)')
     ap.add_argument('--option', action='append', default=[], metavar='KEY=VALUE', help='hp3d_set_option before the run (repeatable)')
-    ap.add_argument('--no-host-path', action='store_true', help='skip the PCIe-inclusive host_path measurement')
+    ap.add_argument('--no-host-path', action='store_true', help='skip the PCIe-inclusive host_path measurement (of --full)')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help="skip the `other_configs` leg (BASELINE.json's other configurations, measured after the primary line)")
+                    help="skip the `other_configs` leg of --full (BASELINE.json's other configurations, measured after the primary line)")
     ap.add_argument('--no-pin', action='store_true', help='do not pin this rank to the CPUs of its GPU\'s NUMA node')
     return ap.parse_args()
 
@@ -523,6 +534,40 @@ def pin_to_gpu_numa(device):
         return None
 
 
+DUMP_MAX_BYTES = 60 * 1000 * 1000          # array bytes of one --dump-outputs: with the .npy headers, under 64 MB either way it is counted
+
+
+def timed_outputs(eng, workload, B, d_coord, d_kphw, d_kpmap, d_sm, gathered):
+    """What the timed path's caller receives from its last step, read back from the device buffers: the 3-D keypoints, the 2-D
+    keypoints in the image and the 256x256 keypoint heat-maps of the full path (every 4th row and column of the first images that
+    fit the budget: the whole map is 176 MB at B = 32), or PoseNet2D's three 32x32 heat-map stages; at N > 1 also the keypoints
+    every rank received from the per-step gather."""
+    if workload == 'full':
+        per_image = 64 * 64 * 21 * 4
+        n = max(1, min(B, (DUMP_MAX_BYTES - B * 63 * 4 - B * 42 * 8 - (0 if gathered is None else gathered.nbytes)) // per_image))
+        out = {'keypoint_coord3d': eng.to_host(d_coord, (B, 21, 3)),
+               'keypoints_hw': eng.to_host(d_kphw, (B, 21, 2), np.float64),
+               'keypoints_scoremap_s4': eng.to_host(d_kpmap, (n, 256, 256, 21))[:, ::4, ::4, :]}
+    else:
+        n = max(1, min(B, DUMP_MAX_BYTES // (3 * 32 * 32 * 21 * 4)))
+        out = {'scoremap_stage%d' % (i + 1): eng.to_host(d_sm[i], (n, 32, 32, 21)) for i in range(3)}
+    if gathered is not None:
+        out['keypoint_coord3d_gathered'] = np.asarray(gathered, np.float32)
+    return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float32 / float64 only, at most DUMP_MAX_BYTES in all."""
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError('--dump-outputs: %s is %s, not float32 / float64' % (name, v.dtype))
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(v))
+
+
 def main():
     a = parse()
     # ROCr reads its flags when the HIP runtime initialises (the first HIP call of the process, hp3d_device_count included): the
@@ -618,34 +663,43 @@ def main():
     for _ in range(a.warmup):
         step()
     # ---- the timed region: profiling off (no per-launch events; hipGraph replay, if asked for, really replays) ----------
-    # The region of EXACTLY K steps (barrier + device sync on both sides, max over ranks) is run REPEATS times back to back and the MEDIAN
-    # region is the one reported (one 0.24 s sample cannot resolve the 0.5 % steps the tuning log works with;
-    # box-to-box spread is +-1.5 %); `value_min` / `value_max` carry the other two.
+    # A region of EXACTLY K steps (barrier + device sync on both sides, max over ranks).  With --full it is run REPEATS times back to back
+    # and the MEDIAN region is the one reported (one 0.24 s sample cannot resolve the 0.5 % steps the tuning
+    # log works with; box-to-box spread is +-1.5 %); `value_min` / `value_max` carry the other two.
     eng.set_profiling(0)
-    REPEATS = 3
+    REPEATS = 3 if a.full else 1
     region_dt = []
+    last = None
     for _ in range(REPEATS):
         rdzv.barrier()
         eng.sync()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step()
+            last = step()
         eng.sync()
         rdzv.barrier()
         region_dt.append(rdzv.max(time.perf_counter() - t0))
     dt = sorted(region_dt)[REPEATS // 2]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, timed_outputs(eng, a.workload, B, d_coord, d_kphw, d_kpmap, d_sm, last))
 
-    # ---- separate profiled pass: HIP events around every launch on the engine stream, accumulated over K steps ----------
-    eng.set_profiling(2)
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    eng.sync()
-    dt_prof = time.perf_counter() - t1
-    rows = eng.profile()
-    eng.set_profiling(0)
+    # ---- separate profiled pass (--full, --layers): HIP events around every launch on the engine stream, accumulated over K steps
+    rows = None
+    if a.full or a.layers:
+        eng.set_profiling(2)
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        eng.sync()
+        dt_prof = time.perf_counter() - t1
+        rows = eng.profile()
+        eng.set_profiling(0)
 
     if rank == 0:
+        roof = others = None
+        workload_str = ("ColorHandPose3DNetwork.inference, %dx%dx3 f32 in HBM, %d images/GPU/step" % (H, W, B)) \
+            if a.workload == 'full' else ("inference_pose2d, 256x256x3 f32 in HBM, %d images/GPU/step" % B)
+    if rank == 0 and rows is not None:
         fam, total_ms = families(rows)
         peak = PEAK_F32_MFMA_TFLOPS if a.dtype == 'f32' else PEAK_F16_MFMA_TFLOPS
 
@@ -669,8 +723,6 @@ def main():
                             "after the structurally zero planes) where the launch fills the chip, else as nine 3x3 blocks on conv_wino4.hip "
                             "(289/784); frac is the executed matrix-core rate over the dense f32 MFMA peak, achieved_algorithmic the "
                             "direct-form FLOPs over the same time")
-        workload_str = ("ColorHandPose3DNetwork.inference, %dx%dx3 f32 in HBM, %d images/GPU/step" % (H, W, B)) \
-            if a.workload == 'full' else ("inference_pose2d, 256x256x3 f32 in HBM, %d images/GPU/step" % B)
         roof["traffic"], roof["traffic_source"] = traffic_record(dom, workload_str, a.dtype)
         roof["timing"] = "HIP events on the engine stream around each launch, separate pass of %d steps (%.3f ms/step profiled)" % (
             a.steps, dt_prof / a.steps * 1e3)
@@ -686,10 +738,11 @@ def main():
                 print("%-28s %-34s %9.3f %9.1f %9.0f" % (name, kern, ms_ / a.steps, fl_ / ms_ / 1e9 if ms_ else 0,
                                                          by_ / ms_ / 1e6 if ms_ else 0), file=sys.stderr)
 
-        # ---- PCIe-inclusive rate (never `value`): pinned host frames in -> 3-D + 2-D keypoints out on the host, the upload
+    if rank == 0:
+        # ---- PCIe-inclusive rate (never `value`, --full): pinned host frames in -> 3-D + 2-D keypoints out on the host, the upload
         #      of batch n+1 overlapped with the kernels of batch n (hp3d_upload_async on a second stream) ------------------
         host_path = None
-        if world == 1 and a.workload == 'full' and not a.no_host_path:
+        if a.full and world == 1 and a.workload == 'full' and not a.no_host_path:
             pin = [eng.pinned_empty((B, H, W, 3)) for _ in range(2)]
             dev = [d_img, eng.dev_alloc(B * H * W * 3 * 4)]
             for p in pin:
@@ -737,16 +790,16 @@ def main():
                                          "[B,21,2] on the host, blocking call per step, two different batches alternating (SURVEY 8d's metric as written)")
             host_path["host_u8_batches_differ"] = bool(len(seen) == 2 and not np.array_equal(seen[0], seen[1]))
 
-        # BASELINE.json's other configurations: GPU measurements first (see other_configs_measure), their oracle spot checks after the CPU leg
+        # BASELINE.json's other configurations (--full): GPU measurements first (see other_configs_measure), their oracle spot checks after the CPU leg
         oc = oc_keep = None
         oc_wall = 0.0
-        if world == 1 and a.workload == 'full' and a.dtype == 'f32' and not a.no_other_configs:
+        if a.full and world == 1 and a.workload == 'full' and a.dtype == 'f32' and not a.no_other_configs:
             t_oc = time.perf_counter()
             oc, oc_keep = other_configs_measure(eng, weights, a, local)
             oc_wall = time.perf_counter() - t_oc
 
         cpu = parity = None
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             gpu_out = {'coord3d': eng.to_host(d_coord, (B, 21, 3)) if a.workload == 'full' else None}
             if a.workload == 'full':
                 eng.infer_full_dev(B, H, W, int(d_img), int(d_hs), kpmap=int(d_kpmap), coord3d=int(d_coord))
@@ -770,9 +823,12 @@ def main():
             "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": a.dtype, "data": "synthetic (seeded images, seeded fan-in-scaled weights)",
             "config": {"workload": workload_str,
-                       "headline": "`value` = inputs resident in HBM when the timed region starts, the MEDIAN of three K-step regions (value_min / "
-                                   "value_max: the other two); SURVEY 8d's metric as written -- host arrays in, keypoints out -- from uint8 frames is "
-                                   "`value_host_u8` (= host_path.value_host_u8), from float32 frames host_path.value",
+                       "headline": ("`value` = inputs resident in HBM when the timed region starts, the MEDIAN of three K-step regions (value_min / "
+                                    "value_max: the other two); SURVEY 8d's metric as written -- host arrays in, keypoints out -- from uint8 frames is "
+                                    "`value_host_u8` (= host_path.value_host_u8), from float32 frames host_path.value") if a.full else
+                                   ("`value` = inputs resident in HBM when the timed region starts, one region of K steps; --full adds two more "
+                                    "regions (value = the median of the three), host_path / value_host_u8, roofline, other_configs and the CPU leg"),
+                       "full": bool(a.full),
                        "global_batch": B * world, "per_gpu_batch": B, "height": H, "width": W,
                        "parallelism": "batch-shard x%d, one process per GPU, no data-path collective; weights by hp3d_bcast_weights "
                                       "and a per-step keypoint all-gather (RCCL through the C ABI, TCP rendezvous; no torch)" % world,

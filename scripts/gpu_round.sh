@@ -31,6 +31,6 @@ cd $R
 # profiles/; the committed files are regenerated from the merged gpurun_out/ by the same script), then take the bench line
 python scripts/summarize_prof.py $OUT $TAG > /dev/null 2>&1
 echo "== bench"
-timeout 900 python bench.py --gpus 1 --steps 10 --warmup 3 --layers > $OUT/bench.json 2> $OUT/bench_layers.txt
+timeout 900 python bench.py --gpus 1 --steps 10 --warmup 3 --full --layers > $OUT/bench.json 2> $OUT/bench_layers.txt
 echo "bench exit $?"; cat $OUT/bench.json
 find $OUT -name "*.csv" | head -20

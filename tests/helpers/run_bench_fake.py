@@ -45,6 +45,7 @@ class FakeLib(object):
 
 class FakeEngine(object):
     log = []
+    full_calls = 0          # infer_full_dev calls of this process (bench.py's steps of the full workload)
 
     def __init__(self, device=0, path=None):
         if os.environ.get('HP3D_FAKE_DIE_RANK') == os.environ.get('RANK', '-'):
@@ -115,6 +116,7 @@ class FakeEngine(object):
         pass
 
     def infer_full_dev(self, *a, **k):
+        FakeEngine.full_calls += 1
         time.sleep(0.002)
 
     def sync(self):
@@ -140,4 +142,5 @@ _lib.Engine = FakeEngine
 _lib.device_count = lambda path=None: int(os.environ.get('HP3D_FAKE_DEVICES', '64'))     # (the stand-in box has as many devices as a test says)
 sys.argv = ['bench.py'] + sys.argv[1:]
 runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='__main__')
+FakeEngine.log.append('full_calls %d' % FakeEngine.full_calls)
 sys.stderr.write('FAKELOG rank %s: %s\n' % (os.environ.get('RANK', '-'), ' | '.join(FakeEngine.log)))

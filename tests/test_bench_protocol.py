@@ -30,7 +30,7 @@ def test_bench_protocol_multi_rank(world):
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
         procs.append(subprocess.Popen([sys.executable, HELPER, '--gpus', str(world), '--steps', '3', '--warmup', '1', '--batch', '2',
-                                       '--height', '16', '--width', '16'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       '--height', '16', '--width', '16', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se[-3000:]
@@ -99,7 +99,7 @@ def test_bench_protocol_rccl_init_that_never_returns_has_a_deadline(hang):
 def test_bench_protocol_single_process_plain():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     out = subprocess.run([sys.executable, HELPER, '--steps', '2', '--warmup', '0', '--batch', '2', '--height', '16', '--width', '16',
-                          '--cpu-seconds', '0'], env=env, capture_output=True, text=True, timeout=300)
+                          '--cpu-seconds', '0', '--full'], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     assert rec['n_gpus'] == 1 and rec['host_path'] is not None
@@ -122,10 +122,78 @@ def test_bench_protocol_single_process_plain():
 def test_bench_other_configs_can_be_switched_off():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     out = subprocess.run([sys.executable, HELPER, '--steps', '1', '--warmup', '0', '--batch', '2', '--height', '16', '--width', '16',
-                          '--cpu-seconds', '0', '--no-other-configs', '--no-host-path'], env=env, capture_output=True, text=True, timeout=300)
+                          '--cpu-seconds', '0', '--no-other-configs', '--no-host-path', '--full'], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     assert 'other_configs' not in rec and rec['host_path'] is None
+    assert rec['roofline'] is not None and rec['timed_regions'] == 3      # (the rest of --full still runs)
+
+
+def _plain_env():
+    return {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT',
+                                                            'HP3D_RDZV_SECRET', 'HP3D_BENCH_ENTRY')}
+
+
+def test_bench_plain_run_times_exactly_the_steps_asked_for():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: W warm-up steps, ONE region of exactly K timed steps, the line -- no
+    second or third region, no profiled pass, no host_path, no other configurations, no CPU leg (all of them --full)."""
+    out = subprocess.run([sys.executable, HELPER, '--gpus', '1', '--steps', '5', '--warmup', '2', '--batch', '2', '--height', '16',
+                          '--width', '16'], env=_plain_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in rec, k
+    assert rec['steps'] == 5 and rec['warmup'] == 2 and rec['timed_regions'] == 1 and rec['config']['full'] is False
+    assert rec['value'] > 0 and rec['ms_per_step'] > 0 and rec['unit'] == 'images/s' and rec['higher_is_better'] is True
+    assert abs(rec['value'] - 2 * 1000.0 / rec['ms_per_step']) <= 0.01 * rec['value']
+    assert rec['roofline'] is None and rec['host_path'] is None and rec['cpu_baseline'] is None and rec['epe_vs_oracle'] is None
+    assert 'other_configs' not in rec
+    log = [l for l in out.stderr.splitlines() if l.startswith('FAKELOG')][0]
+    assert 'full_calls 7' in log, log                 # 2 warm-up + 5 timed: nothing else ran the pipeline
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, one float32 / float64 .npy per array, within 64 MB."""
+    import numpy as np
+    d = tmp_path / 'out'
+    out = subprocess.run([sys.executable, HELPER, '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '3', '--height', '16',
+                          '--width', '16', '--dump-outputs', str(d)], env=_plain_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    files = sorted(os.listdir(d))
+    assert files == ['keypoint_coord3d.npy', 'keypoints_hw.npy', 'keypoints_scoremap_s4.npy'], files
+    arrs = {f: np.load(os.path.join(d, f)) for f in files}
+    assert arrs['keypoint_coord3d.npy'].shape == (3, 21, 3) and arrs['keypoint_coord3d.npy'].dtype == np.float32
+    assert arrs['keypoints_hw.npy'].shape == (3, 21, 2) and arrs['keypoints_hw.npy'].dtype == np.float64
+    assert arrs['keypoints_scoremap_s4.npy'].shape == (3, 64, 64, 21) and arrs['keypoints_scoremap_s4.npy'].dtype == np.float32
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    rec = json.loads(out.stdout.strip().splitlines()[-1])
+    assert rec['steps'] == 2
+    # PoseNet2D workload: its three heat-map stages
+    d2 = tmp_path / 'pose'
+    out = subprocess.run([sys.executable, HELPER, '--gpus', '1', '--steps', '1', '--warmup', '0', '--batch', '2', '--workload', 'posenet',
+                          '--dump-outputs', str(d2)], env=_plain_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert sorted(os.listdir(d2)) == ['scoremap_stage1.npy', 'scoremap_stage2.npy', 'scoremap_stage3.npy']
+    assert np.load(os.path.join(d2, 'scoremap_stage3.npy')).shape == (2, 32, 32, 21)
+
+
+def test_bench_dump_outputs_budget_at_a_large_batch():
+    """The heat-map sample is cut to the first images that fit: the whole dump stays within 64 MB at any batch."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Eng(object):
+        def to_host(self, buf, shape, dtype=np.float32, offset_bytes=0):
+            return np.zeros(shape, dtype)
+    for B in (1, 32, 256, 1024):
+        out = bench.timed_outputs(Eng(), 'full', B, 0, 0, 0, None, None)
+        assert sum(v.nbytes for v in out.values()) <= bench.DUMP_MAX_BYTES, B
+        assert out['keypoint_coord3d'].shape[0] == B and out['keypoints_scoremap_s4'].shape[0] >= min(B, 100)
 
 
 def test_bench_self_launch_spawns_the_ranks():
