@@ -311,7 +311,7 @@ struct hp3d_ctx {
     int fuse12 = 1;            // half-precision trunks: conv1_1 computed inside conv1_2's patch stage (option "f16_fuse12": 0 | 1 = form by size |
                                // 2 = "ring": two workgroups per CU, filter ring | 3 = "resident": one per CU, conv1_2's filters in registers)
     long conv_h16_first_resident_launches = 0;
-    long conv_h16_launches = 0;                     // hp3d_get_counter: layers that went to conv_h16.hip (the child context counts its own)
+    long conv_h16_launches = 0;                     // hp3d_get_counter: layers that went to conv_h16.hip (+ the child context's, as for every whole-path counter)
     int use_wino4 = -2;        // conv_wino4.hip (Winograd F(4x4,3x3)), option "wino4": -2 auto (both trunks by cost model), -1 "pose" (PoseNet2D only, by cost
                                // model), 0 never, 1 wherever eligible (tests)
     int use_wino4s = 0;        // conv_wino4s.hip (F(4x4,3x3) on the bf16 matrix pipe, split operands), option "wino4_split": 0 never, -1 "auto" (the filled
@@ -2655,8 +2655,8 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
     const std::string k(name);
     if (k == "graph_captures") { *value = ctx->graph_captures; return 0; }
     if (k == "graph_replays") { *value = ctx->graph_replays; return 0; }
-    if (k == "conv_h16_launches") { *value = ctx->conv_h16_launches; return 0; }
-    if (k == "conv_h16_first_resident_launches") { *value = ctx->conv_h16_first_resident_launches; return 0; }
+    if (k == "conv_h16_launches") { *value = ctx->conv_h16_launches + (ctx->kid ? ctx->kid->conv_h16_launches : 0); return 0; }
+    if (k == "conv_h16_first_resident_launches") { *value = ctx->conv_h16_first_resident_launches + (ctx->kid ? ctx->kid->conv_h16_first_resident_launches : 0); return 0; }
     if (k == "first_touch_launches") { *value = ctx->first_touch_launches + (ctx->kid ? ctx->kid->first_touch_launches : 0); return 0; }
     if (k == "conv_first_launches") { *value = ctx->conv_first_launches + (ctx->kid ? ctx->kid->conv_first_launches : 0); return 0; }
     if (k == "lift_overlap_calls") { *value = ctx->lift_overlap_calls; return 0; }

@@ -76,7 +76,9 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            480x640, two chunks of 32 at 240x320 / 320x320; 3 M until round 6) or, round 6, for 40 <= B < 64 in float32 mode (a full
  *                            chunk followed by a latency-bound remainder on one stream: B = 40 2487 -> 2616 images/s), else 1 (round 4: with "wino4_tail" the one-stream run no longer
  *                            loses a partial last round, and halves of 16 images fill the chip worse).  Results equal "1" to
- *                            rounding (images are independent; a half may take the small-batch kernel plan);
+ *                            rounding (images are independent; a half may take the small-batch kernel plan).  So within
+ *                            32 < B < 64 (float32; auto = 2 from B = 40 at <= 320x320) an image's results depend on the call's
+ *                            total B: to rounding, and through det pixels on the knife edge also in its mask / crop;
  *                            profiling / graph replay use one stream.  The halves overlap on the device-pointer entry points
  *                            (hp3d_infer_full_dev ...); with HOST output buffers the first half's pageable device->host
  *                            copies block the host before the second half is enqueued;
@@ -312,7 +314,9 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "lift_overlap_calls" = lifting stages that ran their two towers on two streams (option "lift_overlap");
  * "lift_fused_launches" = lifting stages that ran as the one fused launch (option "lift_fused"); "comm_ranks" = ranks of the live RCCL communicator as RCCL itself
- * reports them (ncclCommCount), 0 without one -- bench.py prints it so that a multi-GPU line proves its own world size. */
+ * reports them (ncclCommCount), 0 without one -- bench.py prints it so that a multi-GPU line proves its own world size.
+ * The kernel counters of the whole path ("conv_*", "first_touch_launches", "lift_fused_launches", "fc_tail_launches") include the
+ * launches of the second stream's half (option "streams"); "graph_*" and "lift_overlap_calls" count calls of this context. */
 int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value);
 
 /* ---- multi-GPU: one process and one context per GPU, RCCL over xGMI ---------

@@ -78,3 +78,123 @@ def test_config_c5_f16_480x640_against_oracle_fixture(gpu_engine, synth_weights)
         gpu_engine.set_option('f16_impl', 'h16')
         gpu_engine.load_weight_dict(synth_weights)
         gpu_engine.finalize_weights(0)
+
+
+def test_config_c5_b128_two_streams_against_oracle_fixture(synth_weights):
+    """Config 5 at its SHIPPED batch: B = 128 at 480x640 on f16 trunks, where the default policy runs the call as two halves of 64 on
+    two HIP streams (the second on the child context), without micro-batching, with the filter-resident fused first block -- and, with
+    "f16_fuse12" = "0", conv1_1 on conv_first.hip cut into image ranges at 54 images (5 GB of halves would pass 32-bit offsets).
+    The 16 frames of bench.py's C5 line are tiled 8x and the fixture's two frames are written again at 126 / 127: fixture copies sit at
+    the start of both halves (0 / 1, 64 / 65) and at the very end, and every range cut has copies of a frame on both sides.  Held:
+    the fixture's gates at every fixture copy, every copy bit-equal to its first copy, the mask stage exact, the launch counters of
+    both streams, and the one-stream / unfused / ring variants of the same call.  Own engine: the 25 GB arena goes with it."""
+    import time
+    from hand3d_amd import _lib
+    assert os.path.exists(_lib.DEFAULT_LIB), "libhp3d.so not built (python -m hand3d_amd.build)"
+    g = np.load(FIX)
+    B, H, W = 128, 480, 640
+    frames = synth.make_batch(int(g['seed0']), 16, H, W)           # frames 0 / 1 are the fixture's two images
+    src = np.tile(np.arange(16), B // 16)
+    src[126:128] = [0, 1]
+    x = frames[src]
+    hs = synth.hand_sides(B)                                         # alternating: every copy of a frame has the frame's hand side
+    first = np.array([int(np.argmax(src == f)) for f in src])        # position of each position's first copy
+    fix_pos = [p for p in range(B) if src[p] < 2]
+    assert {0, 1, 64, 65, 126, 127} <= set(fix_pos)
+    keys = ('scoremap', 'mask', 'center', 'scale', 'crop', 'kpmap', 'coord3d')
+    counters = ('conv_h16_launches', 'conv_h16_first_resident_launches', 'conv_first_launches')
+    eng = _lib.Engine(0, path=_lib.DEFAULT_LIB)
+    try:
+        eng.load_weight_dict(synth_weights)
+        eng.finalize_weights('f16')
+
+        def call():
+            c0 = [eng.counter(k) for k in counters]
+            t0 = time.perf_counter()
+            o = eng.infer_full(x, hs, want_mask=True)
+            t = time.perf_counter() - t0
+            return o, dict(zip(counters, [eng.counter(k) - c for k, c in zip(counters, c0)])), t
+
+        def bit_equal(a, b):
+            return all(np.array_equal(a[k], b[k]) for k in keys)
+
+        o, d, t_def = call()
+        assert all(np.isfinite(o[k]).all() for k in keys)
+        # ---- the fixture's gates at every fixture copy (tests above: 2 images; these run on both streams and at the batch's end)
+        det_ref = np.unpackbits(g['det'], axis=1)[:, :H * W].reshape(2, H, W).astype(bool)
+        sure = g['margin_q'].astype(np.float32) * 1e-4 >= 2 * TOL
+        e_kp = e_3d = e_3d_f32 = 0.0
+        for p in fix_pos:
+            f = src[p]
+            det = o['scoremap'][p, ..., 1] > o['scoremap'][p, ..., 0]
+            assert np.array_equal(det[sure[f]], det_ref[f][sure[f]]), "position %d: a det pixel with a decidable margin differs from the oracle" % p
+            assert np.array_equal(o['center'][p], g['center'][f]) and np.array_equal(o['scale'][p], g['scale_crop'][f]), \
+                "position %d took another crop than the oracle's" % p
+            e_kp = max(e_kp, float(np.abs(o['kpmap'][p, ::8, ::8] - g['sm32'][2][f]).max()))
+            e_3d = max(e_3d, float(np.abs(o['coord3d'][p] - g['coord3d'][f]).max()))
+            e_3d_f32 = max(e_3d_f32, float(np.abs(o['coord3d'][p] - g['coord3d_f32'][f]).max()))
+        assert e_kp < TOL and e_3d < 1.2e-3 and e_3d_f32 < 1.5e-3
+        # ---- images are independent: every copy of a frame (other half, other stream, either side of a conv_first range cut, the
+        #      batch's last positions) is bit-equal to its first copy -- no stage may depend on where in the batch an image sits
+        for k in keys:
+            moved = [p for p in range(B) if not np.array_equal(o[k][p], o[k][first[p]])]
+            assert not moved, "%s: positions %s differ from their frame's first copy" % (k, moved[:8])
+        # ---- mask growth / box / centre / scale exact on the device's own score map: each frame once, and both sides of the halves' seam
+        sel = sorted(set(first.tolist()) | {63, 64, 126, 127})
+        m = G.single_obj_scoremap(o['scoremap'][sel], early_exit=True)
+        cen, _, best = G.calc_center_bb(m)
+        assert np.array_equal(o['mask'][sel], m[..., 0])
+        assert np.array_equal(o['center'][sel], cen) and np.array_equal(o['scale'][sel], G.scale_from_crop_size(best, 256))
+        # ---- run to run
+        o_again, d_again, t_again = call()
+        assert bit_equal(o, o_again), "two identical B = 128 calls differ"
+        del o_again
+        # ---- one stream: one launch of 128 images per layer.  HandSegNet, the mask stage and the crop take the same plan at 64 and 128
+        #      images: bit-identical.  PoseNet2D's three float32 score-map heads (conv5_2, conv6_7, conv7_7: 128 -> 21) split their channel
+        #      sum at 64 images and not at 128 (the small-batch plan, hp3d.h "streams"), so stage 1 differs by float32 rounding; stages 2
+        #      and 3 read that map back as halves, where a value next to a half-precision rounding boundary moves by a half ulp and the
+        #      trunk carries it on -- MI355X: stage 1 3.6e-7, heat-maps 7.6e-4, coord3d 3.3e-4.  So stage 1 is held to float32 rounding
+        #      on the same crops, and the heat-maps / 3-D keypoints to the fixture's half-precision gates.
+        eng.set_option('streams', '1')
+        o1, d1, t1 = call()
+        assert all(np.array_equal(o[k], o1[k]) for k in ('scoremap', 'mask', 'center', 'scale', 'crop'))
+        e1 = {k: float(np.abs(o[k] - o1[k]).max()) for k in ('kpmap', 'coord3d')}
+        same1 = bit_equal(o, o1)
+        assert e1['kpmap'] < TOL and e1['coord3d'] < 1.2e-3, e1
+        sm128 = eng.posenet2d(o['crop'])
+        sm64 = eng.posenet2d(o['crop'][64:])
+        e_st = [float(np.abs(a[64:] - b).max()) for a, b in zip(sm128, sm64)]
+        assert e_st[0] < 2e-5 and max(e_st) < TOL, e_st
+        # ... and with conv1_1 on conv_first.hip: one launch of 128 cut at 54 / 108 (documented bit-identical to the fused block)
+        eng.set_option('f16_fuse12', '0')
+        o1u, d1u, _ = call()
+        assert bit_equal(o1, o1u), "f16_fuse12=0 (conv_first range cuts 54 / 108) differs from the fused block"
+        del o1, o1u
+        eng.set_option('streams', 'auto')
+        # ---- two streams, conv1_1 on conv_first.hip: each half of 64 cut at 54 (positions 54 / 118)
+        o_u, d_u, _ = call()
+        assert bit_equal(o, o_u), "f16_fuse12=0 (conv_first range cuts 54 / 118) differs from the fused block"
+        del o_u
+        # ---- the fused block's ring form
+        eng.set_option('f16_fuse12', 'ring')
+        o_r, d_r, _ = call()
+        assert bit_equal(o, o_r), "f16_fuse12=ring differs from the resident form"
+        del o_r
+        print("C5 B=128 480x640 f16 vs oracle fixture at positions %s: heat-map %.2e, coord3d %.2e (vs the float32 oracle %.2e); every copy "
+              "bit-equal to its first; mask stage exact on %d images; one stream: heat-maps %.2e, coord3d %.2e, bit-identical %s (PoseNet2D "
+              "64 vs 128 images per stage %s); f16_fuse12=0 / ring bit-identical; call %.3f s (again %.3f s, one stream %.3f s, host outputs)"
+              % (fix_pos, e_kp, e_3d, e_3d_f32, len(sel), e1['kpmap'], e1['coord3d'], same1, ' / '.join('%.2e' % e for e in e_st), t_def, t_again, t1))
+        print("counters per call: default %s, again %s, one stream %s, f16_fuse12=0 one stream %s / two streams %s, ring %s" % (d, d_again, d1, d1u, d_u, d_r))
+        # ---- launch counters: whole-path counters include the child context's launches (both streams)
+        assert d['conv_h16_first_resident_launches'] == 4, "HandSegNet + PoseNet2D fused block on each of the two streams: %r" % d
+        assert d1['conv_h16_first_resident_launches'] == 2, d1
+        # both halves of 64 and the whole 128 fill the chip: each half runs every layer the whole one does on conv_h16.hip
+        assert d['conv_h16_launches'] == 2 * d1['conv_h16_launches'] > 0, (d, d1)
+        assert d_again == d
+        assert d['conv_first_launches'] == 0 and d_u['conv_first_launches'] == 4 and d1u['conv_first_launches'] == 2, (d, d_u, d1u)
+        assert d_u['conv_h16_first_resident_launches'] == 0 and d_u['conv_h16_launches'] == d['conv_h16_launches'], d_u
+        assert d_r['conv_h16_first_resident_launches'] == 0 and d_r['conv_h16_launches'] == d['conv_h16_launches'], d_r
+    finally:
+        eng.set_option('streams', 'auto')
+        eng.set_option('f16_fuse12', '1')
+        eng.close()

@@ -1425,6 +1425,61 @@ def test_two_streams_equal_one_stream(net, synth_weights):
         eng.set_option('streams', 'auto')
 
 
+def test_stream_policy_follows_the_batch_size(net, synth_weights):
+    """streams=auto between one and two full chunks (round 6, engine.hip:infer_full_chunked): float32 at <= 320x320 takes two halves
+    from B = 40 and one stream of 32 + remainder below.  B = 40 on auto is bit-identical to "2" (that is the plan it took) and B = 39
+    to "1" (the edge of the rule).  Against the one-stream run (chunks of 32 + 8) the halves of 20 give the same results to rounding:
+    the mask stage is exact on each run's own score map, a mask may only move through det pixels whose logit margin is within
+    twice the float gate, and the floats agree wherever mask, centre and scale do."""
+    eng = net.engine
+    B = 40
+    img = synth.make_batch(8600, B, 320, 320)
+    hs = synth.hand_sides(B)
+
+    def run(streams, n):
+        eng.set_option('streams', streams)
+        return eng.infer_full(img[:n], hs[:n], want_mask=True)
+
+    def bit_equal(a, b):
+        return all(np.array_equal(a[k], b[k]) for k in a)
+
+    try:
+        auto, two, one = run('auto', B), run('2', B), run('1', B)
+        auto39, one39 = run('auto', B - 1), run('1', B - 1)
+    finally:
+        eng.set_option('streams', 'auto')
+    assert bit_equal(auto, two), "B = 40 at 320x320 on streams=auto did not take the two-stream plan"
+    assert bit_equal(auto39, one39), "B = 39 at 320x320 on streams=auto did not take the one-stream plan"
+    for o in (two, one):
+        m = G.single_obj_scoremap(o['scoremap'], early_exit=True)
+        cen, _, best = G.calc_center_bb(m)
+        assert np.array_equal(o['mask'], m[..., 0]), "mask growth differs from the oracle's on the device's own score map"
+        assert np.array_equal(o['center'], cen) and np.array_equal(o['scale'], G.scale_from_crop_size(best, 256))
+    e_sm = float(np.abs(two['scoremap'] - one['scoremap']).max())
+    assert e_sm < 2e-5, e_sm                   # HandSegNet does not depend on the crop: every image
+    margin = np.abs(one['scoremap'][..., 1] - one['scoremap'][..., 0])
+    flips = G.fg_and_detmap(two['scoremap'])[1] != G.fg_and_detmap(one['scoremap'])[1]
+    assert (margin[flips] < 4e-5).all(), "a det pixel with a logit margin of %.2e flipped between the plans" % float(margin[flips].max())
+    moved = [i for i in range(B) if not np.array_equal(two['mask'][i], one['mask'][i])]
+    for i in moved:
+        assert flips[i].any(), "image %d: the mask moved without a det pixel flipping" % i
+    same = [i for i in range(B) if i not in moved and np.array_equal(two['center'][i], one['center'][i]) and np.array_equal(two['scale'][i], one['scale'][i])]
+    e = max([float(np.abs(two[k][same] - one[k][same]).max()) for k in ('crop', 'kpmap', 'coord3d')])
+    print("B = 40, 320x320: two streams vs one: score maps %.2e, crop / heat-maps / coord3d %.2e on %d/%d images with the same crop, "
+          "%d det flips (margins < %.2e), bit-identical %s" % (e_sm, e, len(same), B, int(flips.sum()), float(margin[flips].max()) if flips.any() else 0.0,
+                                                                bit_equal(two, one)))
+    assert e < 2e-5 and len(same) >= 36
+
+
+def test_inference2d_batch32_equals_inference(net):
+    """inference2d (hp3d_infer_2d, config 3's own entry point) at config 3's batch: the four maps of the whole-path call, bit for bit."""
+    img = synth.make_batch(3200, 32, 320, 320)
+    hs = synth.hand_sides(32)
+    o = net.inference(img, hs, True)
+    kp, crop, scale, center = net.inference2d(img)
+    assert np.array_equal(kp, o[4]) and np.array_equal(crop, o[1]) and np.array_equal(scale, o[2]) and np.array_equal(center, o[3])
+
+
 def test_conv_first_batch_beyond_32bit_offsets(net, synth_weights):
     """conv1_1 at 480x640 with 28 images writes 2.2 GB: conv_first's launcher cuts the batch into image ranges that each stay
     inside the kernel's 32-bit offsets (config 5 runs 128 images per GPU; hp3d_handsegnet does not chunk the batch itself).

@@ -37,7 +37,8 @@ def _mask_gate(o, i, mask_packed, scoremap_sub, knife_yx):
       * always: the mask STAGE is exact on the device's own score map (seed, growth, box, centre, scale == oracle/general.py on o['scoremap']);
       * the mask equals the reference's -> True (every crop-dependent gate applies to this image);
       * else every det pixel that differs from the reference's det map must be one of the knife-edge pixels the fixture lists
-        (|p_fg - 1/2| < 4e-6 in the reference's own run, scripts/make_tf_fixtures.py:knife_edge_pixels) -> False (its crop moved: skip them)."""
+        (|p_fg - 1/2| < 4e-6 in the reference's own run, scripts/make_tf_fixtures.py:knife_edge_pixels) -> False (its crop moved: the
+        crop-dependent gates then run from the reference's crop, _from_the_reference_crop)."""
     from oracle import general as G
     from oracle import tf_ops as T
     H, W = o['mask'].shape[1:3]
@@ -55,6 +56,27 @@ def _mask_gate(o, i, mask_packed, scoremap_sub, knife_yx):
     stray = [tuple(int(v) for v in p) for p in diff if (int(p[0]), int(p[1])) not in allowed]
     assert len(diff) > 0 and not stray, "image %d: hand mask differs and det pixels %s are not knife-edge pixels of the reference run" % (i, stray[:5])
     return False
+
+
+def _from_the_reference_crop(engine, img1, hand_side, center, scale, crop_sub, sm32, coord3d, kp_crop, kp_uv):
+    """The stages behind the mask for an image whose mask moved through a knife-edge pixel (_mask_gate -> False): its own crop is not the
+    reference's, so they start from the REFERENCE's centre / scale instead -- crop, PoseNet2D heat-maps, 3-D keypoints, arg-max keypoints
+    and their image coordinates under the same gates as every other image.  hp3d_pose3d's first output is coord_xyz_rel_normed, the
+    reference's keypoint_coord3d (nets/ColorHandPose3DNetwork.py:221-247; held to the oracle's `rel` in
+    tests/test_gpu_parity.py::test_pose3d_and_poseprior_variants).  Run on every image, so that this path is exercised whether or not
+    a knife edge moved a mask in this run."""
+    from hand3d_amd.utils.general import trafo_coords
+    crop = engine.crop_and_resize(img1, center, scale, 256)
+    assert np.abs(crop[0, ::8, ::8, :] - crop_sub).max() < 1e-5
+    sm = engine.posenet2d(crop)[-1]
+    e_map = float(np.abs(sm[0] - sm32).max())
+    rel, _, _ = engine.pose3d(sm, hand_side)
+    e_3d = float(np.abs(rel - coord3d).max())
+    assert e_map < TOL_HEATMAP and e_3d < TOL_KP3D, (e_map, e_3d)
+    kp = engine.detect_keypoints(sm)[0]
+    assert np.array_equal(kp, kp_crop)
+    assert np.array_equal(trafo_coords(kp, center, scale, 256), kp_uv)
+    return e_map, e_3d
 
 
 @pytest.fixture(scope='module')
@@ -77,6 +99,9 @@ def test_reference_fixtures_full_pipeline_c1(net, gold):
         hs = g[k + 'hand_side']
         o = net.engine.infer_full(img, hs, want_mask=True)
         assert np.abs(o['scoremap'][0, ::8, ::8, :] - g[k + 'hand_scoremap_sub']).max() < TOL_HEATMAP
+        e_map, err3d = _from_the_reference_crop(net.engine, img, hs, g[k + 'center'], g[k + 'scale_crop'], g[k + 'image_crop_sub'],
+                                                g[k + 'scoremap32'], g[k + 'keypoint_coord3d'], g[k + 'kp_crop'], g[k + 'kp_uv'])
+        print("seed %d: from the reference's crop: heat-map err %.2e, coord3d err %.2e" % (s, e_map, err3d))
         if not _mask_gate(o, 0, g[k + 'mask_packed'], g[k + 'hand_scoremap_sub'], g[k + 'knife_iyx'][:, 1:]):
             undecided.append(int(s))
             continue
@@ -127,6 +152,10 @@ def test_reference_fixtures_batch8_on_the_headline_kernel(net, gold):
     ok = [i for i in range(8) if _mask_gate(o, i, g['mask_packed'][i], g['hand_scoremap_sub'][i], knife[knife[:, 0] == i][:, 1:])]
     print("batch of 8: masks equal to the reference's on images %s (the others moved through a knife-edge pixel)" % ok)
     assert len(ok) >= 6
+    for i in range(8):
+        e_map, e_3d = _from_the_reference_crop(net.engine, img[i:i + 1], hs[i:i + 1], g['center'][i:i + 1], g['scale_crop'][i:i + 1], g['image_crop_sub'][i],
+                                               g['scoremap32'][i], g['keypoint_coord3d'][i:i + 1], g['kp_crop'][i], g['kp_uv'][i])
+        print("batch of 8, image %d%s: from the reference's crop: heat-map err %.2e, coord3d err %.2e" % (i, '' if i in ok else ' (knife edge)', e_map, e_3d))
     assert np.array_equal(o['center'][ok], g['center'][ok]) and np.array_equal(o['scale'][ok], g['scale_crop'][ok])
     assert np.abs(o['crop'][ok][:, ::8, ::8, :] - g['image_crop_sub'][ok]).max() < 1e-5
     e_map = np.abs(o['kpmap'][ok][:, ::8, ::8, :] - g['scoremap32'][ok]).max()

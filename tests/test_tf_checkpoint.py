@@ -101,6 +101,39 @@ def test_snapshot_feeds_the_engine_loader(tmp_path, emu_engine, synth_weights):
     assert emu_engine.nets_mask() & 15 == 15
 
 
+@pytest.mark.gpu
+def test_snapshot_feeds_the_engine_loader_gpu(tmp_path, gpu_engine, synth_weights):
+    """The same snapshot path on the real engine: a retrained snapshot (optimizer slots, global step) read back with the reference's
+    discard list and loaded with init_from_dict computes what the weights loaded straight from the dictionary compute, bit for bit.
+    Another weight set is loaded in between, so a tensor the snapshot path dropped or misnamed could not hide behind a stale one."""
+    from hand3d_amd import ColorHandPose3DNetwork, synth
+    snap = dict(synth_weights)
+    snap['global_step'] = np.array(7, np.int64)
+    for k in list(synth_weights)[:5]:
+        snap[k + '/Adam'] = np.zeros_like(synth_weights[k])
+        snap[k + '/Adam_1'] = np.zeros_like(synth_weights[k])
+    snap['beta1_power'] = np.array(0.9, np.float32)
+    prefix = C.write_bundle(str(tmp_path / 'snapshots' / 'model-1'), snap)
+    w = C.load_weights_from_snapshot(prefix, discard_list=['Adam', 'global_step', 'beta'])
+    assert set(w) == set(synth_weights)
+    img = synth.make_batch(700, 2, 240, 320)
+    hs = synth.hand_sides(2)
+    net = ColorHandPose3DNetwork(engine=gpu_engine)
+    try:
+        net.init_from_dict(synth_weights)
+        want = gpu_engine.infer_full(img, hs, want_mask=True)
+        net.init_from_dict(synth.make_weights(seed=43))
+        other = gpu_engine.infer_full(img, hs, want_mask=True)
+        net.init_from_dict(w)
+        got = gpu_engine.infer_full(img, hs, want_mask=True)
+    finally:
+        gpu_engine.load_weight_dict(synth_weights)
+        gpu_engine.finalize_weights(0)
+    assert not np.array_equal(other['coord3d'], want['coord3d'])
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+
+
 def _crc32c_bitwise(data):
     """An independent CRC-32C (reflected polynomial 0x82F63B78, bit by bit): not the module's table / native code."""
     crc = 0xFFFFFFFF
