@@ -334,6 +334,11 @@ struct hp3d_ctx {
     long conv_wino4_launches = 0;                   // hp3d_get_counter: layers that went to conv_wino4.hip
     long conv_wino2_launches = 0;                   // hp3d_get_counter: layers that went to conv_wino2.hip
     long graph_epoch = 0;      // bumped by anything a captured sequence depends on (allocations, weights, options)
+    int mask_grow = 0;         // option "mask_grow": 0 "auto" (mask_grow_kernel where its LDS maps fit, the global-scratch kernel beyond), 1 "lds"
+                               // (the LDS kernel only: larger frames are refused), 2 "global" (the global-scratch kernel at every size)
+    unsigned* d_mgscratch = nullptr;                // the global-scratch kernel's bitmaps, B x mask_grow_global_words(H, W) words
+    size_t mg_words = 0;
+    long mask_grow_global_launches = 0;             // hp3d_get_counter: mask growths on the global-scratch kernel (+ the child context's)
     int micro_batch = -1;      // whole-path calls run in chunks of at most this many images (0: never split; -1 auto:
                                // 32 in float32 mode, no split with half-precision trunks -- measured optima)
     std::vector<ProfRec> prof;
@@ -443,6 +448,11 @@ int find_var(hp3d_ctx* ctx, const std::string& name, const HostVar** out) {
     return 0;
 }
 
+// the mask growth of an H x W frame runs on the global-scratch kernel (option "mask_grow")
+bool mask_grow_global(const hp3d_ctx* ctx, int H, int W) {
+    return ctx->mask_grow == 2 || (ctx->mask_grow == 0 && !mask_grow_lds_fits(H, W));
+}
+
 // ---- arena ---------------------------------------------------------------------------------
 int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
     const size_t px = (size_t)B * std::max((size_t)H * W, (size_t)256 * 256);
@@ -468,6 +478,10 @@ int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
     if ((size_t)B * H * W > ctx->det_bytes) {
         CHK(dev_realloc(ctx, &ctx->d_det, (size_t)B * H * W));
         ctx->det_bytes = (size_t)B * H * W;
+    }
+    if (mask_grow_global(ctx, H, W) && (size_t)B * mask_grow_global_words(H, W) > ctx->mg_words) {
+        CHK(dev_realloc(ctx, &ctx->d_mgscratch, (size_t)B * mask_grow_global_words(H, W)));
+        ctx->mg_words = (size_t)B * mask_grow_global_words(H, W);
     }
     if (B > ctx->capB) {
         CHK(dev_realloc(ctx, &ctx->d_hs, (size_t)B * 2));
@@ -1295,10 +1309,15 @@ int need_nets(hp3d_ctx* ctx, int mask) {
     return 0;
 }
 
+// The frame-size envelope: the largest per-image activation (conv1_1 / conv1_2: H x W x 64 floats) must stay below 2^31 bytes, the
+// 32-bit offsets the convolution kernels address a chunk with (auto_micro_batch then cuts a call into chunks that keep it) -- up to
+// 8388607 pixels: 2160x3840 is inside.
 int check_img(hp3d_ctx* ctx, int B, int H, int W) {
     if (B < 1 || H < 16 || W < 16)
         HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad shape B=%d H=%d W=%d (need B>=1, H,W >=16)", B, H, W);
-    if (mask_grow_lds_bytes(H, W) > 160 * 1024 - 1024)
+    if ((long)H * W * 64 * 4 >= (1L << 31))
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "image %dx%d too large: H*W*64*4 bytes (one image's largest activation) must stay below 2^31", H, W);
+    if (ctx->mask_grow == 1 && !mask_grow_lds_fits(H, W))
         HP3D_FAIL(ctx, HP3D_ERR_ARG, "image %dx%d too large for the in-LDS mask growth", H, W);
     return 0;
 }
@@ -1325,8 +1344,14 @@ int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W
     }
     {
         ProfScope ps(ctx, "mask_grow", "mask_grow", 0.0, (double)B * H * W);
-        mask_grow_launch(mb, B, H, W, ctx->empty_fltmax, want_mask ? ctx->d_mask : nullptr, ctx->d_center,
-                         ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->stream);
+        if (mask_grow_global(ctx, H, W)) {
+            mask_grow_global_launch(mb, B, H, W, ctx->empty_fltmax, ctx->d_mgscratch, want_mask ? ctx->d_mask : nullptr, ctx->d_center,
+                                    ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->stream);
+            ++ctx->mask_grow_global_launches;
+        } else {
+            mask_grow_launch(mb, B, H, W, ctx->empty_fltmax, want_mask ? ctx->d_mask : nullptr, ctx->d_center,
+                             ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->stream);
+        }
     }
     {
         ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * B * (H * W * 3 + 256 * 256 * 3));
@@ -1482,7 +1507,7 @@ int kid_sync_state(hp3d_ctx* ctx) {
     hp3d_ctx* k = ctx->kid;
     k->blob = ctx->blob; k->blob16 = ctx->blob16; k->nets = ctx->nets; k->prec = ctx->prec;
     k->empty_fltmax = ctx->empty_fltmax; k->conv_naive = ctx->conv_naive; k->use_wino = ctx->use_wino;
-    k->use_first = ctx->use_first; k->first_touch = ctx->first_touch; k->first_balanced = ctx->first_balanced; k->use_wino2 = ctx->use_wino2; k->use_wino4 = ctx->use_wino4; k->fc_tail = ctx->fc_tail; k->tiny_gemm = ctx->tiny_gemm; k->use_wino4s = ctx->use_wino4s; k->w4_tail = ctx->w4_tail; k->use_wino7 = ctx->use_wino7; k->wino7_ksplit = ctx->wino7_ksplit; k->use_pw2 = ctx->use_pw2; k->use_lift_fused = ctx->use_lift_fused; k->use_h16 = ctx->use_h16; k->h16_k7k1 = ctx->h16_k7k1; k->fuse12 = ctx->fuse12; k->wino_splitk = ctx->wino_splitk; k->micro_batch = ctx->micro_batch;
+    k->use_first = ctx->use_first; k->first_touch = ctx->first_touch; k->first_balanced = ctx->first_balanced; k->use_wino2 = ctx->use_wino2; k->use_wino4 = ctx->use_wino4; k->fc_tail = ctx->fc_tail; k->tiny_gemm = ctx->tiny_gemm; k->use_wino4s = ctx->use_wino4s; k->w4_tail = ctx->w4_tail; k->use_wino7 = ctx->use_wino7; k->wino7_ksplit = ctx->wino7_ksplit; k->use_pw2 = ctx->use_pw2; k->use_lift_fused = ctx->use_lift_fused; k->use_h16 = ctx->use_h16; k->h16_k7k1 = ctx->h16_k7k1; k->fuse12 = ctx->fuse12; k->wino_splitk = ctx->wino_splitk; k->micro_batch = ctx->micro_batch; k->mask_grow = ctx->mask_grow;
     k->nstreams = 1; k->profiling = 0; k->use_graph = 0;
     return 0;
 #endif
@@ -1760,6 +1785,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
 #endif
     if (ctx->d_keys) hipFree(ctx->d_keys);
     if (ctx->d_det) hipFree(ctx->d_det);
+    if (ctx->d_mgscratch) hipFree(ctx->d_mgscratch);
     if (ctx->d_u8) hipFree(ctx->d_u8);
     if (ctx->blob16) hipFree(ctx->blob16);
     if (ctx->d_concat16) hipFree(ctx->d_concat16);
@@ -1882,6 +1908,7 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
     }
     if (k == "f16_k7k1" && (v == "0" || v == "1")) { ctx->h16_k7k1 = v == "1"; return 0; }
     if (k == "f16_impl" && (v == "h16" || v == "mfma" || v == "h16_force")) { ctx->use_h16 = v == "mfma" ? 0 : v == "h16" ? 1 : 2; return 0; }
+    if (k == "mask_grow" && (v == "auto" || v == "lds" || v == "global")) { ctx->mask_grow = v == "auto" ? 0 : v == "lds" ? 1 : 2; return 0; }
     if (k == "streams" && (v == "1" || v == "2" || v == "auto")) { ctx->nstreams = v == "auto" ? -1 : v == "2" ? 2 : 1; return 0; }
     if (k == "conv_impl" && (v == "mfma" || v == "naive" || v == "direct" || v == "winograd")) {
         ctx->conv_naive = (v == "naive");
@@ -2575,7 +2602,9 @@ int hp3d_mask_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, 
     if (!ctx) return HP3D_ERR_ARG;
     if (!scoremap || B < 1 || H < 1 || W < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
     if (!(B < H && B < W)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "Scoremap must be [Batch, Width, Height]");  // general.py:210
-    if (mask_grow_lds_bytes(H, W) > 160 * 1024 - 1024) HP3D_FAIL(ctx, HP3D_ERR_ARG, "map too large");
+    if ((long)H * W > (1L << 30)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "map too large (more than 2^30 pixels)");
+    const bool global = mask_grow_global(ctx, H, W);
+    if (!global && !mask_grow_lds_fits(H, W)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "map too large for the in-LDS mask growth");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     Scratch S(ctx);
     const size_t npx = (size_t)B * H * W;
@@ -2590,7 +2619,13 @@ int hp3d_mask_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, 
     float* d_sc = S.alloc<float>(B); NN(ctx, d_sc);
     int* d_seed = S.alloc<int>((size_t)B * 2); NN(ctx, d_seed);
     seg_softmax_launch(d_sm, B, H, W, mb, ctx->stream);
-    mask_grow_launch(mb, B, H, W, ctx->empty_fltmax, d_mask, d_c, d_cs, d_sc, d_seed, ctx->stream);
+    if (global) {
+        unsigned* d_scr = S.alloc<unsigned>((size_t)B * mask_grow_global_words(H, W)); NN(ctx, d_scr);
+        mask_grow_global_launch(mb, B, H, W, ctx->empty_fltmax, d_scr, d_mask, d_c, d_cs, d_sc, d_seed, ctx->stream);
+        ++ctx->mask_grow_global_launches;
+    } else {
+        mask_grow_launch(mb, B, H, W, ctx->empty_fltmax, d_mask, d_c, d_cs, d_sc, d_seed, ctx->stream);
+    }
     if (mask) HIPCHK(ctx, hipMemcpyAsync(mask, d_mask, npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (center) HIPCHK(ctx, hipMemcpyAsync(center, d_c, sizeof(float) * B * 2, hipMemcpyDeviceToHost, ctx->stream));
     if (crop_size) HIPCHK(ctx, hipMemcpyAsync(crop_size, d_cs, sizeof(float) * B, hipMemcpyDeviceToHost, ctx->stream));
@@ -2655,6 +2690,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
     const std::string k(name);
     if (k == "graph_captures") { *value = ctx->graph_captures; return 0; }
     if (k == "graph_replays") { *value = ctx->graph_replays; return 0; }
+    if (k == "mask_grow_global_launches") { *value = ctx->mask_grow_global_launches + (ctx->kid ? ctx->kid->mask_grow_global_launches : 0); return 0; }
     if (k == "conv_h16_launches") { *value = ctx->conv_h16_launches + (ctx->kid ? ctx->kid->conv_h16_launches : 0); return 0; }
     if (k == "conv_h16_first_resident_launches") { *value = ctx->conv_h16_first_resident_launches + (ctx->kid ? ctx->kid->conv_h16_first_resident_launches : 0); return 0; }
     if (k == "first_touch_launches") { *value = ctx->first_touch_launches + (ctx->kid ? ctx->kid->first_touch_launches : 0); return 0; }

@@ -425,6 +425,64 @@ void seg_softmax_kernel(const float* large, int B, int H, int W, unsigned char* 
 // Row r of the bitmap is WW = ceil(W/32) words + ONE zero guard word (pitch P = WW + 1): pixel x is bit x%32 of word x/32; the guard word is
 // the right neighbour of the row's last word and the left neighbour of the next row's first, so the horizontal pass reads its neighbours
 // without knowing its column (round 5: `w % WW` and `u / WW` per word and pass were a third of the pass's instructions).
+// The end of both mask-growth kernels: the [H,W] float mask (optional) from the bitmap `obj` (row pitch P words), and
+// calc_center_bb + scale_from_crop_size (nets/ColorHandPose3DNetwork.py:82-85) from the mask's bounding box (rmax < 0: empty mask).
+// Every thread of the workgroup calls it after the box is final.
+__device__ __forceinline__ void mask_grow_epilogue(const unsigned* obj, int P, int b, int H, int W, int rmin, int rmax, int cmin, int cmax,
+                                                   int sy, int sx, int empty_fltmax, float* mask_out, float* center, float* crop_size,
+                                                   float* scale, int* seed_out) {
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    if (mask_out) {
+        float* mo = mask_out + (size_t)b * H * W;
+        for (int i = tid; i < H * W; i += nthr) {
+            const int y = i / W, x = i - y * W;
+            mo[i] = (obj[y * P + (x >> 5)] >> (x & 31)) & 1u ? 1.f : 0.f;
+        }
+    }
+    if (tid == 0) {
+        float cx, cy, sz;
+        if (rmax >= 0) {
+            const float xmin = (float)rmin, xmax = (float)rmax, ymin = (float)cmin, ymax = (float)cmax;
+            cx = 0.5f * (xmax + xmin);
+            cy = 0.5f * (ymax + ymin);
+            sz = fmaxf(xmax - xmin, ymax - ymin);
+        } else if (empty_fltmax) {   // Eigen-3.3 identities: centre finite (0,0), size -inf -> 100
+            cx = 0.f; cy = 0.f; sz = 100.f;
+        } else {                     // +-inf identities: NaN centre -> (160,160); size -> 100
+            cx = 160.f; cy = 160.f; sz = 100.f;
+        }
+        center[b * 2 + 0] = cx;
+        center[b * 2 + 1] = cy;
+        if (crop_size) crop_size[b] = sz;
+        const float best = sz * 1.25f;                       // nets/ColorHandPose3DNetwork.py:84
+        scale[b] = fminf(fmaxf(256.0f / best, 0.25f), 5.0f);  // :85
+        if (seed_out) { seed_out[b * 2] = sy; seed_out[b * 2 + 1] = sx; }
+    }
+}
+
+// word wx of row y of the packed detmap (d = the image's [H,W] bytes): pixel wx * 32 + k is bit k; wx == WW is the row's zero guard word
+__device__ __forceinline__ unsigned pack_det_word(const unsigned char* d, int y, int wx, int W, int WW) {
+    unsigned bits = 0;
+    const unsigned char* row = d + (size_t)y * W + wx * 32;
+    if (wx == WW) {
+        // guard word
+    } else if (wx * 32 + 32 <= W && ((W & 7) == 0)) {          // 4 aligned 8-byte loads instead of 32 byte loads
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned long long v = *(const unsigned long long*)(row + q * 8);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if ((v >> (8 * k)) & 0xffull) bits |= (1u << (q * 8 + k));
+        }
+    } else {
+        for (int k = 0; k < 32; ++k) {
+            const int x = wx * 32 + k;
+            if (x < W && row[k]) bits |= (1u << k);
+        }
+    }
+    return bits;
+}
+
 constexpr int MG_R = 12;          // rows per thread in the vertical pass of mask_grow
 HP3D_KERNEL(1024)
 void mask_grow_kernel(const unsigned char* det, const unsigned long long* keys, int H, int W, int empty_fltmax,
@@ -444,25 +502,7 @@ void mask_grow_kernel(const unsigned char* det, const unsigned long long* keys, 
 
     for (int w = tid; w < NWORD; w += nthr) {
         const int y = w / P, wx = w - y * P;
-        unsigned bits = 0;
-        const unsigned char* row = d + (size_t)y * W + wx * 32;
-        if (wx == WW) {
-            // guard word
-        } else if (wx * 32 + 32 <= W && ((W & 7) == 0)) {          // 4 aligned 8-byte loads instead of 32 byte loads
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned long long v = *(const unsigned long long*)(row + q * 8);
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if ((v >> (8 * k)) & 0xffull) bits |= (1u << (q * 8 + k));
-            }
-        } else {
-            for (int k = 0; k < 32; ++k) {
-                const int x = wx * 32 + k;
-                if (x < W && row[k]) bits |= (1u << k);
-            }
-        }
-        detb[w] = bits;
+        detb[w] = pack_det_word(d, y, wx, W, WW);
         obj[w] = (y == sy && wx == (sx >> 5)) ? (1u << (sx & 31)) : 0u;
     }
     if (tid == 0) { s_rmin = 0x7fffffff; s_rmax = -1; s_cmin = 0x7fffffff; s_cmax = -1; s_changed[0] = s_changed[1] = 0; obj[-1] = 0u; obj[NWORD] = 0u; }
@@ -551,32 +591,143 @@ void mask_grow_kernel(const unsigned char* det, const unsigned long long* keys, 
         atomicMin(&s_cmin, cmin); atomicMax(&s_cmax, cmax);
     }
     __syncthreads();
-    if (mask_out) {
-        float* mo = mask_out + (size_t)b * H * W;
-        for (int i = tid; i < H * W; i += nthr) {
-            const int y = i / W, x = i - y * W;
-            mo[i] = (obj[y * P + (x >> 5)] >> (x & 31)) & 1u ? 1.f : 0.f;
-        }
+    mask_grow_epilogue(obj, P, b, H, W, s_rmin, s_rmax, s_cmin, s_cmax, sy, sx, empty_fltmax, mask_out, center, crop_size, scale, seed_out);
+}
+
+// ---------------------------------------------------------------------------------------
+// The same growth for frames whose three bitmaps do not fit one workgroup's LDS (mask_grow_lds_bytes > 159 KB: 540x960 and up).
+// The bitmaps (same layout: pitch P = WW + 1 with the zero guard word) live in a per-image block of global scratch,
+// mask_grow_global_words(H, W) words: det, then obj with its two end guards, then tmp.  mask_pack_kernel fills det and O_0 over the
+// whole chip; mask_grow_global_kernel then runs the passes with one workgroup per image.  One image's maps (0.8 MB at 1080x1920) stay
+// in the L2 of the XCD the workgroup runs on.
+//
+// Active window (exact): O_j is zero outside its bounding box [r0,r1] x [c0,c1], so dilate(O_j) -- and with it O_{j+1} -- is zero
+// outside that box grown by 10 pixels.  A pass therefore forms the horizontal dilation in rows r0..r1 only (zero elsewhere: those rows
+// of obj are empty) and writes obj only on the word columns and rows of the grown box; every word outside it already holds zero in
+// O_j and in O_{j+1}, so the scratch holds exactly O_{j+1} after the pass.  The box of O_{j+1} is collected from the words the pass
+// writes (LDS min / max atomics, as the bounding-box epilogue), so the epilogue needs no scan.  A hand a few hundred pixels across costs
+// what it costs at 320x320, whatever the frame size; the worst case is det all ones (the window spans the frame after max(H,W)/20 passes).
+//
+// Visibility: every word a pass reads was written by another wave of the SAME workgroup before a __syncthreads().  __syncthreads() is a
+// workgroup-scope release fence (each wave waits for its stores: s_waitcnt vmcnt(0)), s_barrier, and a workgroup-scope acquire fence;
+// the waves of a workgroup share one CU and its vector L1 (no threadgroup split mode here), so the AMDGPU memory model needs no cache
+// invalidate at that scope and the loads after the barrier see the stores before it.  No data crosses workgroups: the pack kernel's
+// stores reach this kernel through the kernel boundary on the same stream.
+HP3D_KERNEL(256)
+void mask_pack_kernel(const unsigned char* det, const unsigned long long* keys, int H, int W, unsigned* scratch) {
+    const int WW = (W + 31) >> 5, P = WW + 1, NWORD = H * P;
+    const int b = blockIdx.y;
+    unsigned* detb = scratch + (size_t)b * (3 * (size_t)NWORD + 2);
+    unsigned* obj = detb + NWORD + 1;
+    const unsigned char* d = det + (size_t)b * H * W;
+    const unsigned idx = 0xFFFFFFFFu - (unsigned)(keys[b] & 0xFFFFFFFFull);
+    const int sy = (int)(idx / (unsigned)W), sx = (int)(idx % (unsigned)W);
+    for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < NWORD; w += gridDim.x * blockDim.x) {
+        const int y = w / P, wx = w - y * P;
+        detb[w] = pack_det_word(d, y, wx, W, WW);
+        obj[w] = (y == sy && wx == (sx >> 5)) ? (1u << (sx & 31)) : 0u;
+        if (w == 0) { obj[-1] = 0u; obj[NWORD] = 0u; }
     }
+}
+
+HP3D_KERNEL(1024)
+void mask_grow_global_kernel(const unsigned long long* keys, int H, int W, int empty_fltmax, unsigned* scratch,
+                             float* mask_out, float* center, float* crop_size, float* scale, int* seed_out) {
+    const int WW = (W + 31) >> 5, P = WW + 1;
+    const int NWORD = H * P;
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const unsigned* detb = scratch + (size_t)b * (3 * (size_t)NWORD + 2);
+    unsigned* obj = (unsigned*)detb + NWORD + 1;
+    unsigned* tmp = obj + NWORD + 1;
+    // s_box[k] = {rmin, rmax, cmin, cmax} of O_j, k = j & 1 (O_j's box is read at the top of pass j, O_{j+1}'s collected in it)
+    __shared__ int s_box[2][4], s_changed[2];
+    const unsigned idx = 0xFFFFFFFFu - (unsigned)(keys[b] & 0xFFFFFFFFull);
+    const int sy = (int)(idx / (unsigned)W), sx = (int)(idx % (unsigned)W);
     if (tid == 0) {
-        float cx, cy, sz;
-        if (s_rmax >= 0) {
-            const float xmin = (float)s_rmin, xmax = (float)s_rmax, ymin = (float)s_cmin, ymax = (float)s_cmax;
-            cx = 0.5f * (xmax + xmin);
-            cy = 0.5f * (ymax + ymin);
-            sz = fmaxf(xmax - xmin, ymax - ymin);
-        } else if (empty_fltmax) {   // Eigen-3.3 identities: centre finite (0,0), size -inf -> 100
-            cx = 0.f; cy = 0.f; sz = 100.f;
-        } else {                     // +-inf identities: NaN centre -> (160,160); size -> 100
-            cx = 160.f; cy = 160.f; sz = 100.f;
-        }
-        center[b * 2 + 0] = cx;
-        center[b * 2 + 1] = cy;
-        if (crop_size) crop_size[b] = sz;
-        const float best = sz * 1.25f;                       // nets/ColorHandPose3DNetwork.py:84
-        scale[b] = fminf(fmaxf(256.0f / best, 0.25f), 5.0f);  // :85
-        if (seed_out) { seed_out[b * 2] = sy; seed_out[b * 2 + 1] = sx; }
+        s_box[0][0] = s_box[0][1] = sy; s_box[0][2] = s_box[0][3] = sx;     // O_0 = {seed}
+        if ((unsigned)sy >= (unsigned)H) s_box[0][1] = -1;                  // (no valid seed: nothing grows; the window never leaves the map)
+        s_changed[0] = s_changed[1] = 0;
     }
+    __syncthreads();
+
+    const int num_passes = max(H, W) / 10;   // max(s[1], s[2]) // (filter_size // 2)
+    int cur = 0;                             // s_box[cur] = the box of what obj holds
+    for (int pass = 0; pass < num_passes; ++pass) {
+        const int r0 = s_box[cur][0], r1 = s_box[cur][1], c0 = s_box[cur][2], c1 = s_box[cur][3];
+        // (the next box's slot was last read at the top of the previous pass, before two barriers)
+        if (tid == 0) { s_box[cur ^ 1][0] = 0x7fffffff; s_box[cur ^ 1][1] = -1; s_box[cur ^ 1][2] = 0x7fffffff; s_box[cur ^ 1][3] = -1; }
+        if (r1 < 0) break;                   // O_j empty: so is every later one (uniform: all threads read the same box)
+        const int R0 = max(r0 - 10, 0), R1 = min(r1 + 10, H - 1);
+        const int wx0 = max(c0 - 10, 0) >> 5, wx1 = min(c1 + 10, W - 1) >> 5, nwx = wx1 - wx0 + 1;
+        // horizontal dilation, radius 10, rows r0..r1 of the window's word columns (the guard words make the row ends)
+        const int nh = (r1 - r0 + 1) * nwx;
+        for (int i = tid; i < nh; i += nthr) {
+            const int yy = i / nwx, w = (r0 + yy) * P + wx0 + (i - yy * nwx);
+            const unsigned long long lo = obj[w - 1], mid = obj[w], hi = obj[w + 1];
+            unsigned long long win = (mid << 16) | (lo >> 16) | (hi << 48);
+            win = win | (win << 1) | (win >> 1);     // radius 1
+            win = win | (win << 2) | (win >> 2);     // radius 3
+            win = win | (win << 4) | (win >> 4);     // radius 7
+            win = win | (win << 3) | (win >> 3);     // radius 10
+            tmp[w] = (unsigned)(win >> 16);
+        }
+        __syncthreads();
+        if (tid == 0) s_changed[(pass + 1) & 1] = 0;
+        // vertical dilation, radius 10, AND det, rows R0..R1: as in mask_grow_kernel, MG_R rows of one word column per unit; tmp rows
+        // outside r0..r1 (the rows written above) are zero
+        int changed = 0;
+        int rmin = 0x7fffffff, rmax = -1, cmin = 0x7fffffff, cmax = -1;
+        const int nunits = ((R1 - R0 + MG_R) / MG_R) * nwx;
+        for (int u = tid; u < nunits; u += nthr) {
+            const int seg = u / nwx, wx = wx0 + (u - seg * nwx);
+            const int y0 = R0 + seg * MG_R;
+            unsigned v[MG_R + 20];
+            const int base = (y0 - 10) * P + wx;
+#pragma unroll
+            for (int i = 0; i < MG_R + 20; ++i) {
+                const int y = y0 - 10 + i;
+                v[i] = (y >= r0 && y <= r1) ? tmp[base + i * P] : 0u;
+            }
+            unsigned a2[MG_R + 17], a4[MG_R + 5];
+            {
+                unsigned a1[MG_R + 19];
+#pragma unroll
+                for (int i = 0; i < MG_R + 19; ++i) a1[i] = v[i] | v[i + 1];
+#pragma unroll
+                for (int i = 0; i < MG_R + 17; ++i) a2[i] = a1[i] | a1[i + 2];
+                unsigned a3[MG_R + 13];
+#pragma unroll
+                for (int i = 0; i < MG_R + 13; ++i) a3[i] = a2[i] | a2[i + 4];
+#pragma unroll
+                for (int i = 0; i < MG_R + 5; ++i) a4[i] = a3[i] | a3[i + 8];
+            }
+#pragma unroll
+            for (int j = 0; j < MG_R; ++j) {
+                const int y = y0 + j;
+                if (y <= R1) {
+                    const int w = y * P + wx;
+                    const unsigned acc = (a4[j] | a2[j + 16] | v[j + 20]) & detb[w];     // rows y-10 .. y+10
+                    if (acc != obj[w]) changed = 1;
+                    obj[w] = acc;
+                    if (acc) {
+                        rmin = min(rmin, y); rmax = max(rmax, y);
+                        cmin = min(cmin, wx * 32 + (__ffs(acc) - 1));
+                        cmax = max(cmax, wx * 32 + (31 - __clz(acc)));
+                    }
+                }
+            }
+        }
+        if (rmax >= 0) {
+            atomicMin(&s_box[cur ^ 1][0], rmin); atomicMax(&s_box[cur ^ 1][1], rmax);
+            atomicMin(&s_box[cur ^ 1][2], cmin); atomicMax(&s_box[cur ^ 1][3], cmax);
+        }
+        if (changed) s_changed[pass & 1] = 1;
+        __syncthreads();
+        cur ^= 1;
+        if (!s_changed[pass & 1]) break;
+    }
+    mask_grow_epilogue(obj, P, b, H, W, s_box[cur][0], s_box[cur][1], s_box[cur][2], s_box[cur][3], sy, sx, empty_fltmax, mask_out,
+                       center, crop_size, scale, seed_out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1014,6 +1165,16 @@ void seg_softmax_launch(const float* scoremap_large, int B, int H, int W, const 
 }
 // three bitmaps of H rows x (ceil(W / 32) + 1 guard) words, + the two end guards of the growing one
 size_t mask_grow_lds_bytes(int H, int W) { return ((size_t)3 * H * ((W + 31) / 32 + 1) + 2) * sizeof(unsigned); }
+bool mask_grow_lds_fits(int H, int W) { return mask_grow_lds_bytes(H, W) <= 160 * 1024 - 1024; }
+size_t mask_grow_global_words(int H, int W) { return (size_t)3 * H * ((W + 31) / 32 + 1) + 2; }
+void mask_grow_global_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltmax, unsigned* scratch, float* mask_out,
+                             float* center, float* crop_size, float* scale, int* seed, hipStream_t s) {
+    const long nword = (long)H * ((W + 31) / 32 + 1);
+    HP3D_LAUNCH(mask_pack_kernel, dim3(grid_for(nword, 256, 64), B), dim3(256), 0, s, (const unsigned char*)mb.det,
+                (const unsigned long long*)mb.argmax_key, H, W, scratch);
+    HP3D_LAUNCH(mask_grow_global_kernel, dim3(B), dim3(1024), 0, s, (const unsigned long long*)mb.argmax_key, H, W, empty_fltmax,
+                scratch, mask_out, center, crop_size, scale, seed);
+}
 void mask_grow_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltmax, float* mask_out, float* center,
                       float* crop_size, float* scale, int* seed, hipStream_t s) {
     const size_t smem = mask_grow_lds_bytes(H, W);

@@ -432,6 +432,11 @@ void kp_detect_launch(const float* sm, int B, int h, int w, int C, int cs, int o
 void argmax2d_launch(const float* x, int B, int H, int W, int C, int cs, int* out_rc, hipStream_t s);
 void copy_channels_launch(const float* in, int npix, int C, int in_cs, float* out, int out_cs, hipStream_t s);
 size_t mask_grow_lds_bytes(int H, int W);
+bool mask_grow_lds_fits(int H, int W);           // the three bitmaps fit mask_grow_kernel's LDS
+size_t mask_grow_global_words(int H, int W);     // per-image scratch of mask_grow_global_launch (32-bit words)
+// the same growth with the bitmaps in global scratch (B x mask_grow_global_words words): any frame size
+void mask_grow_global_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltmax, unsigned* scratch, float* mask_out,
+                             float* center, float* crop_size, float* scale, int* seed, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

@@ -65,6 +65,12 @@ const char* hp3d_last_error(hp3d_ctx* ctx);          /* ctx may be NULL: last gl
 void* hp3d_stream(hp3d_ctx* ctx);                    /* the hipStream_t all work is queued on */
 int hp3d_sync(hp3d_ctx* ctx);
 /* options: "empty_reduce" = "inf" | "fltmax" (oracle/general.py EMPTY_REDUCE);
+ *          "mask_grow"    = "auto" (default) | "lds" | "global": the seeded mask growth on bit-packed maps in one workgroup's LDS
+ *                            (mask_grow_kernel; "auto" takes it wherever its three maps fit, 3 * H * (ceil(W / 32) + 1) + 2 words
+ *                            <= 159 KB, e.g. 640x640 or 480x864) or with the maps in global scratch (mask_grow_global_kernel: any
+ *                            frame, e.g. 720x1280, 1080x1920; "auto" beyond the LDS size).  "lds" refuses larger frames
+ *                            (HP3D_ERR_ARG "too large for the in-LDS mask growth"); "global" takes the scratch kernel at every size.
+ *                            Both give the same results bit for bit;
  *          "conv_impl"    = "mfma" (default: direct MFMA kernel, and float32 Winograd F(2x2,3x3) for the stride-1 3x3
  *                            layers with Cout%64==0 and the 7x7 layers -- taken as nine 3x3 blocks -- whenever the grid
  *                            fills the chip, >= 256 work items) | "direct" (never Winograd: bit-identical to an fmaf
@@ -198,7 +204,10 @@ int hp3d_nets_mask(hp3d_ctx* ctx);   /* bit0 HandSegNet, bit1 PoseNet2D, bit2 Po
  *   image [B,H,W,3] (x/255-0.5 done by the caller, run.py:59), hand_side [B,2] one-hot ->
  *   hand_scoremap [B,H,W,2], image_crop [B,256,256,3], scale_crop [B,1], center [B,2] (row,col),
  *   keypoints_scoremap [B,256,256,21], keypoint_coord3d [B,21,3].  Any H, W >= 16 (the VALID 2x2 max-pools floor odd
- *   extents and the logits are resized from floor(H/8) x floor(W/8) back to H x W, as in the reference).
+ *   extents and the logits are resized from floor(H/8) x floor(W/8) back to H x W, as in the reference) with
+ *   H * W * 64 * 4 < 2^31, i.e. at most 8388607 pixels per image (2160x3840 is inside): one image's largest activation must fit
+ *   the 32-bit offsets of the convolution kernels.  Larger frames -> HP3D_ERR_ARG before any launch.  The same holds for
+ *   hp3d_infer_2d*, hp3d_infer_full_u8* (at the network size) and hp3d_handsegnet.
  * hp3d_infer_2d     replaces .inference2d (:101-129): keypoints_scoremap, image_crop, scale_crop, center.
  * hp3d_handsegnet   replaces .inference_detection (:131-168): scoremap_large [B,H,W,2]
  *   (scoremap_small [B,H/8,W/8,2] is the pre-upsampling map, for staged parity tests).
@@ -264,10 +273,9 @@ int hp3d_pose3d(hp3d_ctx* ctx, int B, const float* scoremap32, const float* hand
  * hp3d_resize_bilinear tf.image.resize_images (TF1.3 legacy bilinear)         nets/ColorHandPose3DNetwork.py:97,128,166
  * hp3d_crop_and_resize crop_image_from_xy -> tf.image.crop_and_resize         utils/general.py:163-196
  * hp3d_mask_from_scoremap single_obj_scoremap + calc_center_bb + scale        utils/general.py:233-328, CHP3D.py:82-85
- *                      SIZE LIMIT (the reference has none): the growth runs on bit-packed maps in ONE workgroup's LDS,
- *                      3 * H * (ceil(W / 32) + 1) + 2 words <= 159 KB, e.g. 640x640 or 480x864 (since round 5 each row carries a
- *                      zero guard word: 640x672, accepted before, is refused now); larger maps -> HP3D_ERR_ARG "too large".
- *                      The whole-path entry points (hp3d_infer_full*, hp3d_infer_2d*) have the same limit on the input image.
+ *                      Maps of up to 2^30 pixels: bit-packed maps in one workgroup's LDS where they fit (option "mask_grow",
+ *                      3 * H * (ceil(W / 32) + 1) + 2 words <= 159 KB), in global scratch beyond; larger maps -> HP3D_ERR_ARG
+ *                      "map too large".  With "mask_grow" = "lds" maps beyond the LDS size are refused.
  *                      -> mask [B,H,W], center [B,2], crop_size [B,1] (before *1.25), scale [B,1], seed int32 [B,2]
  * hp3d_fc              NetworkOps.fully_connected(_relu)                      utils/general.py:112-136
  * hp3d_argmax2d        detect_keypoints (per-channel first arg-max)           utils/general.py:331-344
@@ -311,11 +319,13 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "conv_wino4_tail_launches" = those of them whose last round ran as channel slices (option "wino4_tail");
  * "conv_wino7_launches" = 7x7 layers that ran on conv_wino7.hip (option "wino7"), "conv_wino7_split_launches" = those of them in the channel-split form; "conv_pw2_launches" = 1x1 layer pairs that ran as one launch (option "pw2");
  * "first_touch_launches" = read passes in front of conv1_1 (option "first_touch");
+ * "mask_grow_global_launches" = mask growths (one launch per call or chunk, all its images) on the global-scratch kernel (option "mask_grow");
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "lift_overlap_calls" = lifting stages that ran their two towers on two streams (option "lift_overlap");
  * "lift_fused_launches" = lifting stages that ran as the one fused launch (option "lift_fused"); "comm_ranks" = ranks of the live RCCL communicator as RCCL itself
  * reports them (ncclCommCount), 0 without one -- bench.py prints it so that a multi-GPU line proves its own world size.
- * The kernel counters of the whole path ("conv_*", "first_touch_launches", "lift_fused_launches", "fc_tail_launches") include the
+ * The kernel counters of the whole path ("conv_*", "first_touch_launches", "lift_fused_launches", "fc_tail_launches",
+ * "mask_grow_global_launches") include the
  * launches of the second stream's half (option "streams"); "graph_*" and "lift_overlap_calls" count calls of this context. */
 int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value);
 
