@@ -231,9 +231,69 @@ struct ProfRec {
     hipEvent_t e0, e1;
 };
 
+// Everything hp3d_set_option writes.  The second stream's context copies the whole record (kid_sync_state), so an option added
+// here reaches both halves of a two-stream call.
+struct Options {
+    int empty_fltmax = 0;
+    int conv_naive = 0;
+    int use_wino = 1;          // 3x3/s1 layers with Cout%64==0 run as Winograd F(2x2,3x3) (conv_impl=direct disables)
+    int first_touch_beside = 1;     // option "first_touch_beside": the read pass on the child context's stream beside conv1_1 (1) | in front of it (0)
+    int first_touch = -1;      // option "first_touch": stream conv1_1's input image through the memory-side cache right before the launch: -1 auto
+                               // (a cold image of 8 ... 128 MB), 0 never, 1 always
+    int first_balanced = 1;    // option "first_walk": conv_first.hip's workgroups walk balanced runs of tiles ("balanced") | whole tile rows ("rows": rounds 2-4)
+    int use_first = 1;         // conv1_1 on its own kernel (conv_first.hip); conv_impl=direct keeps it on the general one
+    int nstreams = -1;         // whole-path calls: halves of the batch on two HIP streams (option "streams"; -1 auto)
+    int use_h16 = 1;           // half-precision 3x3 trunk layers on conv_h16.hip (option "f16_impl" = "h16" | "mfma")
+    int h16_k7k1 = 1;          // ... and the 7x7 / 1x1 layers with >= 64 couts on its single-buffer forms (option "f16_k7k1" = 0 | 1)
+    int wino_splitk = 1;       // Winograd layers that under-fill the chip split their channel steps (option "wino_splitk")
+    int lift_overlap = 1;      // option "lift_overlap": the two towers of the unfused lifting stage on two streams (ViewpointNet on the child context's)
+    int use_lift_fused = -1;   // the lifting stage as one launch (lift_fused.hip): -1 auto (B <= 4), 0 never, 1 always (option "lift_fused")
+    int use_wino2 = -1;        // conv_wino2.hip (two workgroups per CU): -1 auto (short reductions, under-filled launches), 0 never, 1 wherever eligible (option "wino2")
+    int use_graph = 0;
+    int fuse12 = 1;            // half-precision trunks: conv1_1 computed inside conv1_2's patch stage (option "f16_fuse12": 0 | 1 = form by size |
+                               // 2 = "ring": two workgroups per CU, filter ring | 3 = "resident": one per CU, conv1_2's filters in registers)
+    int use_wino4 = -2;        // conv_wino4.hip (Winograd F(4x4,3x3)), option "wino4": -2 auto (both trunks by cost model), -1 "pose" (PoseNet2D only, by cost
+                               // model), 0 never, 1 wherever eligible (tests)
+    int use_wino4s = 0;        // conv_wino4s.hip (F(4x4,3x3) on the bf16 matrix pipe, split operands), option "wino4_split": 0 never, -1 "auto" (the filled
+                               // 3x3 launches with Cin >= 128 that conv_wino4.hip would take), 1 wherever eligible (tests)
+    int kp_up_side = 1;        // the heat-map up-sampling behind ViewpointNet on the child stream (1) or behind PosePrior on this one (0): option "kp_up_side"
+    int fc_tail = 1;           // the tail of a lifting tower (reduce of the first FC layer + the two small FC layers) as one launch (option "fc_tail")
+    int tiny_gemm = 1;         // the towers' last stride-2 layer (8x8 -> 4x4) as split-K GEMM over its output pixels (option "tiny_gemm")
+    int w4_tail = 1;           // conv_wino4.hip: cut an under-filled last round of items into channel slices (option "wino4_tail")
+    int use_pw2 = 1;           // conv_pw2.hip: the 1x1 head pairs (conv6_1 + conv6_2, conv5_1 + conv5_2, conv6_6 + conv6_7, conv7_6 + conv7_7) as one launch each
+                               // (option "pw2": 0 never, 1 when the launch has a workgroup per CU, 2 = "force": whenever the shapes allow, tests)
+    int use_wino7 = -1;        // conv_wino7.hip (the 7x7 layers as Winograd F(4x4,4x4)), option "wino7": -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
+    int wino7_ksplit = 0;      // option "wino7_ksplit": 0 = auto (conv_wino7_eligible's choice for under-filled launches), N = that many channel splits (tests, tuning)
+    int mask_grow = 0;         // option "mask_grow": 0 "auto" (mask_grow_kernel where its LDS maps fit, the global-scratch kernel beyond), 1 "lds"
+                               // (the LDS kernel only: larger frames are refused), 2 "global" (the global-scratch kernel at every size)
+    int micro_batch = -1;      // whole-path calls run in chunks of at most this many images (0: never split; -1 auto:
+                               // 32 in float32 mode, no split with half-precision trunks -- measured optima)
+};
+
+// Launch counters (hp3d_get_counter: which kernels really ran).
+struct Counters {
+    long conv_first_launches = 0;
+    long first_touch_launches = 0;
+    long lift_overlap_calls = 0;
+    long lift_fused_launches = 0;
+    long graph_captures = 0, graph_replays = 0;     // did the hipGraph path really run?
+    long conv_h16_first_resident_launches = 0;
+    long conv_h16_launches = 0;                     // layers that went to conv_h16.hip
+    long conv_wino4s_launches = 0;
+    long conv_wino4s_tail_launches = 0;
+    long fc_tail_launches = 0, conv_s2_gemm_launches = 0;
+    long conv_pw2_launches = 0;
+    long conv_wino7_launches = 0;
+    long conv_wino7_split_launches = 0;
+    long conv_wino4_tail_launches = 0;
+    long conv_wino4_launches = 0;                   // layers that went to conv_wino4.hip
+    long conv_wino2_launches = 0;                   // layers that went to conv_wino2.hip
+    long mask_grow_global_launches = 0;             // mask growths on the global-scratch kernel
+};
+
 }  // namespace
 
-struct hp3d_ctx {
+struct hp3d_ctx : Options, Counters {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -245,9 +305,6 @@ struct hp3d_ctx {
     hp3d_f16* d_concat16 = nullptr;
     size_t concat16_px = 0;
     int nets = 0;              // finalized nets mask
-    int empty_fltmax = 0;
-    int conv_naive = 0;
-    int use_wino = 1;          // 3x3/s1 layers with Cout%64==0 run as Winograd F(2x2,3x3) (conv_impl=direct disables)
     // debug copies of the unpacked HWIO weights for conv_impl=naive
     std::map<std::string, float*> naive_w;
 
@@ -283,64 +340,16 @@ struct hp3d_ctx {
     struct GraphEntry { hipGraphExec_t exec = nullptr; long epoch = -1; int calls = 0; };
     std::map<std::string, GraphEntry> graphs;    // hp3d_set_option("graph", "1"): replayed whole-call launch sequences
 #endif
-    long conv_first_launches = 0;
-    int first_touch_beside = 1;     // option "first_touch_beside": the read pass on the child context's stream beside conv1_1 (1) | in front of it (0)
-    int first_touch = -1;      // option "first_touch": stream conv1_1's input image through the memory-side cache right before the launch: -1 auto
-                               // (a cold image of 8 ... 128 MB), 0 never, 1 always
     bool trunk_input_hot = false;   // set by run_trunk: the trunk's input was written by the kernel in front of it (crop, uint8 front end)
-    long first_touch_launches = 0;
-    int first_balanced = 1;    // option "first_walk": conv_first.hip's workgroups walk balanced runs of tiles ("balanced") | whole tile rows ("rows": rounds 2-4)
-    int use_first = 1;         // conv1_1 on its own kernel (conv_first.hip); conv_impl=direct keeps it on the general one
-    int nstreams = -1;         // whole-path calls: halves of the batch on two HIP streams (option "streams"; -1 auto)
     hp3d_ctx* kid = nullptr;   // the second stream's context: own stream + arena, SHARES this context's weight blob
     bool shared_weights = false;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int use_h16 = 1;           // half-precision 3x3 trunk layers on conv_h16.hip (option "f16_impl" = "h16" | "mfma")
-    int h16_k7k1 = 1;          // ... and the 7x7 / 1x1 layers with >= 64 couts on its single-buffer forms (option "f16_k7k1" = 0 | 1)
-    int wino_splitk = 1;       // Winograd layers that under-fill the chip split their channel steps (option "wino_splitk")
-    int lift_overlap = 1;      // option "lift_overlap": the two towers of the unfused lifting stage on two streams (ViewpointNet on the child context's)
-    long lift_overlap_calls = 0;
-    int use_lift_fused = -1;   // the lifting stage as one launch (lift_fused.hip): -1 auto (B <= 4), 0 never, 1 always (option "lift_fused")
     unsigned* d_liftbar = nullptr;
     unsigned* h_lifterr = nullptr;     // mapped host word: lift_fused.hip's grid barrier timed out (results of that launch are invalid)
-    long lift_fused_launches = 0;
     bool two_streams_live = false;   // set while a whole-path call runs its two halves on two streams (kernel choice: wino2_auto)
-    int use_wino2 = -1;        // conv_wino2.hip (two workgroups per CU): -1 auto (short reductions, under-filled launches), 0 never, 1 wherever eligible (option "wino2")
-    int use_graph = 0;
-    long graph_captures = 0, graph_replays = 0;     // hp3d_get_counter: did the hipGraph path really run?
-    int fuse12 = 1;            // half-precision trunks: conv1_1 computed inside conv1_2's patch stage (option "f16_fuse12": 0 | 1 = form by size |
-                               // 2 = "ring": two workgroups per CU, filter ring | 3 = "resident": one per CU, conv1_2's filters in registers)
-    long conv_h16_first_resident_launches = 0;
-    long conv_h16_launches = 0;                     // hp3d_get_counter: layers that went to conv_h16.hip (+ the child context's, as for every whole-path counter)
-    int use_wino4 = -2;        // conv_wino4.hip (Winograd F(4x4,3x3)), option "wino4": -2 auto (both trunks by cost model), -1 "pose" (PoseNet2D only, by cost
-                               // model), 0 never, 1 wherever eligible (tests)
-    int use_wino4s = 0;        // conv_wino4s.hip (F(4x4,3x3) on the bf16 matrix pipe, split operands), option "wino4_split": 0 never, -1 "auto" (the filled
-                               // 3x3 launches with Cin >= 128 that conv_wino4.hip would take), 1 wherever eligible (tests)
-    long conv_wino4s_launches = 0;
-    long conv_wino4s_tail_launches = 0;
-    int kp_up_side = 1;        // the heat-map up-sampling behind ViewpointNet on the child stream (1) or behind PosePrior on this one (0): option "kp_up_side"
-    int fc_tail = 1;           // the tail of a lifting tower (reduce of the first FC layer + the two small FC layers) as one launch (option "fc_tail")
-    int tiny_gemm = 1;         // the towers' last stride-2 layer (8x8 -> 4x4) as split-K GEMM over its output pixels (option "tiny_gemm")
-    long fc_tail_launches = 0, conv_s2_gemm_launches = 0;
-    int w4_tail = 1;           // conv_wino4.hip: cut an under-filled last round of items into channel slices (option "wino4_tail")
-    int use_pw2 = 1;           // conv_pw2.hip: the 1x1 head pairs (conv6_1 + conv6_2, conv5_1 + conv5_2, conv6_6 + conv6_7, conv7_6 + conv7_7) as one launch each
-                               // (option "pw2": 0 never, 1 when the launch has a workgroup per CU, 2 = "force": whenever the shapes allow, tests)
-    long conv_pw2_launches = 0;
-    int use_wino7 = -1;        // conv_wino7.hip (the 7x7 layers as Winograd F(4x4,4x4)), option "wino7": -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
-    long conv_wino7_launches = 0;
-    int wino7_ksplit = 0;      // option "wino7_ksplit": 0 = auto (conv_wino7_eligible's choice for under-filled launches), N = that many channel splits (tests, tuning)
-    long conv_wino7_split_launches = 0;
-    long conv_wino4_tail_launches = 0;
-    long conv_wino4_launches = 0;                   // hp3d_get_counter: layers that went to conv_wino4.hip
-    long conv_wino2_launches = 0;                   // hp3d_get_counter: layers that went to conv_wino2.hip
     long graph_epoch = 0;      // bumped by anything a captured sequence depends on (allocations, weights, options)
-    int mask_grow = 0;         // option "mask_grow": 0 "auto" (mask_grow_kernel where its LDS maps fit, the global-scratch kernel beyond), 1 "lds"
-                               // (the LDS kernel only: larger frames are refused), 2 "global" (the global-scratch kernel at every size)
     unsigned* d_mgscratch = nullptr;                // the global-scratch kernel's bitmaps, B x mask_grow_global_words(H, W) words
     size_t mg_words = 0;
-    long mask_grow_global_launches = 0;             // hp3d_get_counter: mask growths on the global-scratch kernel (+ the child context's)
-    int micro_batch = -1;      // whole-path calls run in chunks of at most this many images (0: never split; -1 auto:
-                               // 32 in float32 mode, no split with half-precision trunks -- measured optima)
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -371,11 +380,11 @@ hipEvent_t get_event(hp3d_ctx* ctx) {
     return ctx->event_pool[ctx->event_next++];
 }
 
-struct ProfScope {
+struct ProfScope {          // kernel == nullptr: no profile row
     hp3d_ctx* ctx;
     int idx = -1;
     ProfScope(hp3d_ctx* c, const std::string& name, const char* kernel, double flops, double bytes) : ctx(c) {
-        if (!c->profiling) return;
+        if (!c->profiling || !kernel) return;
         ProfRec r{name, kernel, flops, bytes, get_event(c), get_event(c)};
         hipEventRecord(r.e0, c->stream);
         idx = (int)c->prof.size();
@@ -534,21 +543,33 @@ void same_pad(int in, int k, int stride, int* out, int* before) {
 // of that work each, two run per CU, so its time is the balanced share plus one small item of tail -- it wins where the coarse rounds
 // quantise badly (300 items on 256 CUs) and at small batches, and loses ~7 % on long filled launches (twice the window traffic and
 // input-transform work per MFMA).  `old_nt` / `old_ks`: conv_wino_eligible's answer for the same layer (0: it would not run).
-bool wino2_auto(int k, int cin_pad, int cout_pad, int Ho, int Wo, int B, int old_nt, int old_ks, int ks2, bool two_streams) {
-    if ((long)B * Ho * Wo < 512) return false;              // 16 x 16 maps and below: one direct launch beats split + reduce
-    if (!old_nt) return Ho * Wo >= 900 && cin_pad >= 64;      // trunk layers conv_wino.hip cannot fill; the lifting nets' 16 x 16 / 8 x 8 maps stay direct
-    const double cus = hp3d_num_cus(), reduce_cost = 0.7, c2 = 1.07;
+// conv_wino.hip's time for a layer (`old_nt` / `old_ks` as above).  frac_rounds: the last round of items counts fractionally
+// (wino4_auto with the second stream live); otherwise whole rounds.
+double wino_cost(int k, int cin_pad, int cout_pad, int Ho, int Wo, int B, int old_nt, int old_ks, bool frac_rounds) {
+    const double cus = hp3d_num_cus(), reduce_cost = 0.7;
     const long tiles = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
     const int nsub = k == 7 ? 9 : 1;
     const long items1 = (tiles + old_nt - 1) / old_nt * (cout_pad / (old_nt == 32 ? 128 : 64));
     const int S1 = nsub * cin_pad / (old_nt == 32 ? 32 : 16);
     const double w1 = old_nt == 32 ? 1.0 : 0.5;
-    const double t_old = old_ks > 1 ? std::ceil((double)S1 / old_ks) * w1 * std::max(1.0, items1 * old_ks / cus) + reduce_cost
-                                    : std::ceil(items1 / cus) * S1 * w1;
+    const double rounds = frac_rounds ? std::max(1.0, items1 / cus) : std::ceil(items1 / cus);
+    return old_ks > 1 ? std::ceil((double)S1 / old_ks) * w1 * std::max(1.0, items1 * old_ks / cus) + reduce_cost : rounds * S1 * w1;
+}
+// conv_wino2.hip's time for a layer split `ks2` ways
+double wino2_cost(int k, int cin_pad, int cout_pad, int Ho, int Wo, int B, int ks2) {
+    const double cus = hp3d_num_cus(), reduce_cost = 0.7, c2 = 1.07;
+    const long tiles = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
+    const int nsub = k == 7 ? 9 : 1;
     const long items2 = (tiles + 31) / 32 * (cout_pad / 64);
     const int S2 = nsub * cin_pad / 16;
-    const double t_new = ks2 > 1 ? c2 * (std::ceil((double)S2 / ks2) * 0.25 * std::max(1.0, items2 * ks2 / cus)) + reduce_cost
-                                 : c2 * (items2 * S2 * 0.25 / cus + S2 * 0.125);
+    return ks2 > 1 ? c2 * (std::ceil((double)S2 / ks2) * 0.25 * std::max(1.0, items2 * ks2 / cus)) + reduce_cost
+                   : c2 * (items2 * S2 * 0.25 / cus + S2 * 0.125);
+}
+bool wino2_auto(int k, int cin_pad, int cout_pad, int Ho, int Wo, int B, int old_nt, int old_ks, int ks2, bool two_streams) {
+    if ((long)B * Ho * Wo < 512) return false;              // 16 x 16 maps and below: one direct launch beats split + reduce
+    if (!old_nt) return Ho * Wo >= 900 && cin_pad >= 64;      // trunk layers conv_wino.hip cannot fill; the lifting nets' 16 x 16 / 8 x 8 maps stay direct
+    const double t_old = wino_cost(k, cin_pad, cout_pad, Ho, Wo, B, old_nt, old_ks, false);
+    const double t_new = wino2_cost(k, cin_pad, cout_pad, Ho, Wo, B, ks2);
     // with a second stream on the GPU the other half's kernels fill conv_wino.hip's tail rounds anyway (measured: B = 16 as 8 + 8
     // loses 2 % when its filled layers switch): only under-filled launches are candidates then
     if (two_streams && old_ks <= 1) return false;
@@ -578,22 +599,8 @@ bool wino4_auto(int mode, bool posenet, int k, int cin_pad, int cout_pad, int Ho
     // (7x7 layers 0.85: their split partial sums go through a reduce launch).  With the second stream live the other half's kernels
     // fill tail rounds, so rounds count fractionally.
     auto rounds = [&](double items) { return two_streams ? std::max(1.0, items / cus) : std::ceil(items / cus); };
-    double t_best = 1e30;
-    if (old_nt) {
-        const long tiles = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
-        const long items1 = (tiles + old_nt - 1) / old_nt * (cout_pad / (old_nt == 32 ? 128 : 64));
-        const int S1 = nsub * cin_pad / (old_nt == 32 ? 32 : 16);
-        const double w1 = old_nt == 32 ? 1.0 : 0.5;
-        t_best = old_ks > 1 ? std::ceil((double)S1 / old_ks) * w1 * std::max(1.0, items1 * old_ks / cus) + reduce_cost : rounds((double)items1) * S1 * w1;
-    }
-    {
-        const long tiles = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
-        const long items2 = (tiles + 31) / 32 * (cout_pad / 64);
-        const int S2 = nsub * cin_pad / 16;
-        const double t2 = ks2 > 1 ? 1.07 * (std::ceil((double)S2 / ks2) * 0.25 * std::max(1.0, items2 * ks2 / cus)) + reduce_cost
-                                  : 1.07 * (items2 * S2 * 0.25 / cus + S2 * 0.125);
-        t_best = std::min(t_best, t2);
-    }
+    double t_best = old_nt ? wino_cost(k, cin_pad, cout_pad, Ho, Wo, B, old_nt, old_ks, two_streams) : 1e30;
+    t_best = std::min(t_best, wino2_cost(k, cin_pad, cout_pad, Ho, Wo, B, ks2));
     const long tiles4 = (long)B * ((Ho + 3) / 4) * ((Wo + 3) / 4);
     const long items4 = (tiles4 + 31) / 32 * (cout_pad / 64);
     const int S4 = nsub * cin_pad / 16;
@@ -621,18 +628,206 @@ static int wino2_ks_probe(hp3d_ctx* ctx, const ConvL& l, int Ho, int Wo, int B, 
     return ks;
 }
 
-// ---- one convolution layer -------------------------------------------------------------------
-// in: [B,H,W,in_cs] (engine channels start at `in`), out: [B,Ho',Wo',out_cs] channel 0 at `out`.
-// f16 = 1 (trunk nets after hp3d_finalize_weights(dtype=1)): `in` / `out` hold halves (except the raw image of
-// conv1_1 and out_f32 heads); in_cs / out_cs are then counted in ELEMENTS of the respective tensor.
 int kid_sync_state(hp3d_ctx* ctx);
 
+// Work forked onto the child context's stream (after kid_sync_state): the child's stream starts after everything already queued on
+// this context's (inputs produced there), and whatever happens after the fork, the join is recorded and waited for on EVERY exit path
+// -- this context's stream must not run ahead of (and hp3d_sync / hp3d_dev_free / hp3d_destroy must cover) what was enqueued on the
+// child's.  two_streams: the two halves of a whole-path call (two_streams_live is set on both contexts until the join).
+struct KidFork {
+    hp3d_ctx* ctx = nullptr;
+    bool two_streams = false;
+    int fork(hp3d_ctx* c, bool two = false) {
+#ifndef HP3D_EMU
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->kid->stream, c->ev_fork, 0));
+        ctx = c;
+        two_streams = two;
+        if (two) c->two_streams_live = c->kid->two_streams_live = true;
+        return 0;
+#else
+        HP3D_FAIL(c, HP3D_ERR_UNSUPPORTED, "no second stream in the CPU interpreter build");
+#endif
+    }
+    ~KidFork() {
+#ifndef HP3D_EMU
+        if (!ctx) return;
+        hp3d_ctx* k = ctx->kid;
+        if (two_streams) ctx->two_streams_live = k->two_streams_live = false;
+        if (hipEventRecord(ctx->ev_join, k->stream) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
+        else (void)hipStreamSynchronize(k->stream);
+#endif
+    }
+};
+
+// ---- one convolution layer -------------------------------------------------------------------
 static int wino7_ks_override(const hp3d_ctx* ctx, int ks, int cin_pad, long out_floats) {        // option "wino7_ksplit"
     if (ctx->wino7_ksplit <= 0 || !ctx->wino_splitk) return ks;
     ks = std::min(ctx->wino7_ksplit, cin_pad / 16);
     return (ks >= 2 && ks * out_floats * 4 < (1L << 31)) ? ks : 1;
 }
 
+// The ConvParams fields every form of a layer sets; each form then sets what differs (tiles, ksplit, nsub, im2col, f16, partial).
+ConvParams conv_params(const float* in, const float* wpk, const float* bias, float* out, int B, int H, int W, int Ho, int Wo, int Cin, int in_cs,
+                       int Cout, int out_cs, int cout_store, int pad_t, int pad_l, int act) {
+    ConvParams p;
+    p.in = in; p.wpk = wpk; p.bias = bias; p.out = out;
+    p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
+    p.Cin = Cin; p.in_cs = in_cs; p.Cout = Cout; p.out_cs = out_cs; p.cout_store = cout_store;
+    p.pad_t = pad_t; p.pad_l = pad_l; p.act = act;
+    p.tiles_x = 0; p.tiles_y = 0; p.ksplit = 1; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.im2col = 0; p.nsub = 1;
+    return p;
+}
+
+// Grows the scratch of split-K partial sums / tail pieces (launches still queued may read the old buffer: synchronise first).
+int ensure_col(hp3d_ctx* ctx, size_t floats) {
+    if (floats > ctx->col_floats) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        CHK(dev_realloc(ctx, &ctx->col, floats));
+        ctx->col_floats = floats;
+    }
+    return 0;
+}
+
+// The reduce behind a channel-split launch: ctx->col = [ks][B*Ho*Wo][cout_pad] raw sums -> bias + activation (+ the layer's 2x2
+// max-pool) -> out.  profile = false: no profile row (conv_mfma's reduce never had one).
+void splitk_reduce(hp3d_ctx* ctx, const ConvL& l, int ks, int B, int Ho, int Wo, int pool, float* out, int out_cs, bool profile = true) {
+    ProfScope ps(ctx, l.name, !profile ? nullptr : pool ? "conv_splitk_reduce_pool" : "conv_splitk_reduce", 0.0, 4.0 * (ks + 1) * B * Ho * Wo * l.cout_pad);
+    if (pool)
+        conv_splitk_reduce_pool_launch(ctx->col, ks, B, Ho, Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
+    else
+        conv_splitk_reduce_launch(ctx->col, ks, (long)B * Ho * Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
+}
+
+// The Winograd kernel a layer takes, decided before anything is launched.
+enum WinoKind { WINO_NONE, WINO7, WINO4S, WINO4, WINO2, WINO };
+struct WinoPick {
+    WinoKind kind = WINO_NONE;
+    size_t w_off = 0;          // its packed filters in the blob
+    int ks = 1;                // channel splits (> 1: raw partial sums to ctx->col, then splitk_reduce)
+    std::string kernel;        // the profile row's kernel name
+};
+
+WinoPick pick_wino(hp3d_ctx* ctx, const ConvL& l, int in_cs, int out_cs, int B, int Ho, int Wo, int pool, int f16) {
+    if (!ctx->use_wino || f16) return {};
+    auto take = [&](WinoKind kind, size_t off, int ks, const char* stem) {
+        return WinoPick{kind, off, ks, std::string(stem) + (l.k == 7 ? (ks > 1 ? "_as7x7_splitk" : "_as7x7") : ks > 1 ? "_splitk" : pool ? "_pool" : "")};
+    };
+    int wino_ks = 1, wino2_ks = 1, wino4_ks = 1, ks7 = 1;
+    const int old_nt = l.ww_off ? conv_wino_eligible(ctx->use_wino, l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool,
+                                                     ctx->wino_splitk ? &wino_ks : nullptr) : 0;
+    // 7x7 layers (PoseNet2D's refinement units): Winograd F(4x4,4x4) over the filter's four 4x4-tap blocks when the launch fills the chip
+    // (one work item = a 4x4 tile block x 64 couts, no channel split: 160 of 256 CUs busy already beats the split nine-block form + its reduce)
+    // (under-filled launches -- small batches -- split the 16-channel chunks over workgroups and add the raw sums in a reduce launch, like the other
+    //  Winograd kernels: option "wino_splitk")
+    long items7 = 0;
+    if (ctx->use_wino7 && l.ww7_off && !pool && !ctx->conv_naive &&
+        conv_wino7_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, &items7, ctx->wino_splitk ? &ks7 : nullptr)) {
+        ks7 = wino7_ks_override(ctx, ks7, l.cin_pad, (long)B * Ho * Wo * l.cout_pad);
+        if (ctx->use_wino7 == 1 || items7 >= (long)hp3d_num_cus() * 5 / 8 || (ks7 > 1 && ctx->use_wino7 == -1 && !ctx->two_streams_live))
+            return take(WINO7, l.ww7_off, ks7, "conv_wino7_f4x4_4x4");
+    }
+    const bool take4 = ctx->use_wino4 && l.ww4_off && !ctx->conv_naive &&
+        conv_wino4_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, ctx->wino_splitk ? &wino4_ks : nullptr) &&
+        (ctx->use_wino4 == 1 ||
+         (ctx->use_wino4 < 0 && wino4_auto(ctx->use_wino4, l.net == NET_POSE, l.k, l.cin_pad, l.cout_pad, Ho, Wo, B, wino4_ks, old_nt, wino_ks,
+                                           wino2_ks_probe(ctx, l, Ho, Wo, B, in_cs, out_cs, pool), ctx->two_streams_live)));
+    // round 6: the filled 3x3 launches with Cin >= 128 on the bf16 matrix pipe with split operands (conv_wino4s.hip), option "wino4_split"
+    int filled4s = 0;
+    if (ctx->use_wino4s && l.ww4s_off && !ctx->conv_naive && l.k == 3 &&
+        conv_wino4s_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, &filled4s) &&
+        (ctx->use_wino4s == 1 || (take4 && wino4_ks <= 1 && filled4s)))
+        return take(WINO4S, l.ww4s_off, 1, "conv_wino4s_f4x4_3x3_bf16x3");
+    if (take4) return take(WINO4, l.ww4_off, wino4_ks, "conv_wino4_f4x4_3x3");
+    if (ctx->use_wino2 && l.ww2_off && !ctx->conv_naive &&
+        conv_wino2_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, ctx->wino_splitk ? &wino2_ks : nullptr) &&
+        (ctx->use_wino2 == 1 || wino2_auto(l.k, l.cin_pad, l.cout_pad, Ho, Wo, B, old_nt, wino_ks, wino2_ks, ctx->two_streams_live)))
+        return take(WINO2, l.ww2_off, wino2_ks, "conv_wino2_f2x2_3x3");
+    if (old_nt) return take(WINO, l.ww_off, wino_ks, "conv_wino_f2x2_3x3");
+    return {};
+}
+
+// Launches the Winograd form `w` of layer l; p = the layer's common parameters with w's filters.  All forms share one protocol: a
+// channel split writes raw partial sums at conv resolution to ctx->col and the pool (if any) happens in the reduce.
+int run_wino(hp3d_ctx* ctx, const ConvL& l, const WinoPick& w, ConvParams p, int pool, double flops, double bytes) {
+    float* const out = p.out;
+    const int out_cs = p.out_cs, B = p.B, Ho = p.Ho, Wo = p.Wo;
+    p.ksplit = w.ks;
+    p.nsub = w.kind == WINO7 ? 4 : l.k == 7 ? 9 : 1;
+    if (w.kind == WINO) { p.tiles_x = (Wo + 15) / 16; p.tiles_y = (Ho + 7) / 8; }
+    if (w.ks > 1) {        // under-filled chip: channel steps split over workgroups
+        CHK(ensure_col(ctx, (size_t)w.ks * B * Ho * Wo * l.cout_pad));
+        p.out = ctx->col; p.out_cs = l.cout_pad; p.cout_store = l.cout_pad;
+    } else if ((w.kind == WINO4 || w.kind == WINO4S) && l.k == 3 && ctx->w4_tail && conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
+        // an under-filled last round of items runs as channel slices, one piece per CU (conv_wino4.hip, TAIL): scratch for the raw sums
+        CHK(ensure_col(ctx, w.kind == WINO4 ? conv_wino4_tail_floats() : conv_wino4s_tail_floats()));
+        p.partial = ctx->col; p.partial_cap = ctx->col_floats;
+    }
+    {
+        ProfScope ps(ctx, l.name, w.kernel.c_str(), flops, bytes);
+        const int lpool = w.ks > 1 ? 0 : pool;
+        // (the F(4x4,3x3) launchers answer 1 when the last round really ran as tail pieces: the counters are the tests' proof)
+        int lr;
+        switch (w.kind) {
+        case WINO7:
+            if (conv_wino7_launch(p, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,4x4)): launch refused");
+            ++ctx->conv_wino7_launches;
+            ctx->conv_wino7_split_launches += w.ks > 1;
+            break;
+        case WINO4S:
+            if ((lr = conv_wino4s_launch(p, lpool, ctx->stream)) < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,3x3), split operands): launch refused");
+            ++ctx->conv_wino4s_launches;
+            ctx->conv_wino4s_tail_launches += lr == 1;
+            break;
+        case WINO4:
+            if ((lr = conv_wino4_launch(p, lpool, ctx->stream)) < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,3x3)): launch refused");
+            ++ctx->conv_wino4_launches;
+            ctx->conv_wino4_tail_launches += lr == 1;
+            break;
+        case WINO2:
+            if (conv_wino2_launch(p, lpool, ctx->stream) < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (2 workgroups per CU): launch refused");
+            ++ctx->conv_wino2_launches;
+            break;
+        default:
+            if (conv_wino_launch(p, lpool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv: tensor exceeds 32-bit offsets");
+        }
+    }
+    if (w.ks > 1) splitk_reduce(ctx, l, w.ks, B, Ho, Wo, pool, out, out_cs);
+    return 0;
+}
+
+// conv1_1 on its own kernel (conv_first.hip); p = the layer's parameters
+int run_conv_first(hp3d_ctx* ctx, const ConvL& l, const ConvParams& p, double flops, double bytes) {
+    const size_t px = (size_t)p.B * p.H * p.W;
+    // A COLD input image (the caller's device buffer, an upload: not written by the kernel in front of this one) costs this
+    // store-bound kernel a third of its rate -- its gathers run one tile ahead, an HBM miss takes longer than a tile (round 5: 3.5
+    // TB/s in the pipeline against 4.8 standalone and for PoseNet2D's freshly written crop).  Streaming the image once through the
+    // memory-side cache first (13 us for 39 MB) takes B = 32 at 320 x 320 from 0.253 to 0.175 ms (5.0 TB/s = 0.63 of the HBM spec).
+    const size_t img_bytes = px * 12;
+    // The pass runs on the child context's stream BESIDE the convolution (it is ahead of the gathers after the first few tiles and
+    // needs 16 registers per wave next to the convolution's 3 x 160): its 13 us disappear; in this stream when there is no second one.
+    KidFork beside;            // (joined when this function returns: the call's completion covers the read pass)
+    if (ctx->d_keys && (ctx->first_touch == 1 || (ctx->first_touch < 0 && !ctx->trunk_input_hot && img_bytes >= (8u << 20) && img_bytes <= (128u << 20)))) {
+        if (ctx->first_touch_beside && !ctx->use_graph && !ctx->shared_weights && !ctx->two_streams_live && kid_sync_state(ctx) == 0) {
+            CHK(beside.fork(ctx));          // (whatever produced the image on this stream comes first)
+            touch_launch(p.in, px * 3, (float*)ctx->d_keys, ctx->kid->stream);
+        } else {
+            ProfScope pt(ctx, l.name, "conv_first_touch", 0.0, 0.0);
+            touch_launch(p.in, px * 3, (float*)ctx->d_keys, ctx->stream);
+        }
+        ++ctx->first_touch_launches;
+    }
+    {
+        ProfScope ps(ctx, l.name, p.f16 ? "conv_first_3x3_c3_f16" : "conv_first_3x3_c3", flops, bytes);
+        conv_first_launch(p, ctx->stream, ctx->first_balanced);
+    }
+    ++ctx->conv_first_launches;
+    return 0;
+}
+
+// in: [B,H,W,in_cs] (engine channels start at `in`), out: [B,Ho',Wo',out_cs] channel 0 at `out`.
+// f16 = 1 (trunk nets after hp3d_finalize_weights(dtype=1)): `in` / `out` hold halves (except the raw image of
+// conv1_1 and out_f32 heads); in_cs / out_cs are then counted in ELEMENTS of the respective tensor.
 int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, int H, int W, float* out, int out_cs,
              int pool, int* Ho_out, int* Wo_out, int f16 = 0, int out_f32 = 0) {
     int Ho, Wo, pt, pl;
@@ -652,232 +847,22 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
         if (Wo_out) *Wo_out = Wo;
         return 0;
     }
-    int wino_ks = 1, wino2_ks = 1;
-    const int old_nt = (ctx->use_wino && !f16 && l.ww_off) ? conv_wino_eligible(ctx->use_wino, l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool,
-                                                                                 ctx->wino_splitk ? &wino_ks : nullptr) : 0;
-    // 7x7 layers (PoseNet2D's refinement units): Winograd F(4x4,4x4) over the filter's four 4x4-tap blocks when the launch fills the chip
-    // (one work item = a 4x4 tile block x 64 couts, no channel split: 160 of 256 CUs busy already beats the split nine-block form + its reduce)
-    // (under-filled launches -- small batches -- split the 16-channel chunks over workgroups and add the raw sums in a reduce launch, like the other
-    //  Winograd kernels: option "wino_splitk")
-    long items7 = 0;
-    int ks7 = 1;
-    const bool take7 = ctx->use_wino && ctx->use_wino7 && !f16 && l.ww7_off && !pool && !ctx->conv_naive &&
-        conv_wino7_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, &items7, ctx->wino_splitk ? &ks7 : nullptr) &&
-        ((ks7 = wino7_ks_override(ctx, ks7, l.cin_pad, (long)B * Ho * Wo * l.cout_pad)), true) &&
-        (ctx->use_wino7 == 1 || items7 >= (long)hp3d_num_cus() * 5 / 8 || (ks7 > 1 && ctx->use_wino7 == -1 && !ctx->two_streams_live));
-    if (take7) {
-        ConvParams p;
-        p.in = in; p.wpk = ctx->blob + l.ww7_off; p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = in_cs; p.Cout = l.cout_pad; p.out_cs = out_cs;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = l.relu; p.im2col = 0; p.ksplit = ks7; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.nsub = 4;
-        if (ks7 > 1) {
-            const size_t need = (size_t)ks7 * B * Ho * Wo * l.cout_pad;
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-            p.out = ctx->col; p.out_cs = l.cout_pad; p.cout_store = l.cout_pad;
-        }
-        {
-            ProfScope ps(ctx, l.name, ks7 > 1 ? "conv_wino7_f4x4_4x4_as7x7_splitk" : "conv_wino7_f4x4_4x4_as7x7", flops, bytes);
-            if (conv_wino7_launch(p, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,4x4)): launch refused");
-        }
-        if (ks7 > 1) {
-            ProfScope ps(ctx, l.name, "conv_splitk_reduce", 0.0, 4.0 * (ks7 + 1) * B * Ho * Wo * l.cout_pad);
-            conv_splitk_reduce_launch(ctx->col, ks7, (long)B * Ho * Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs,
-                                      std::min(l.cout_pad, out_cs), ctx->stream);
-        }
-        ++ctx->conv_wino7_launches;
-        ctx->conv_wino7_split_launches += ks7 > 1;
-        HIPCHK(ctx, hipGetLastError());
-        if (Ho_out) *Ho_out = Ho;
-        if (Wo_out) *Wo_out = Wo;
-        return 0;
-    }
-    int wino4_ks = 1;
-    const bool take4 = ctx->use_wino && ctx->use_wino4 && !f16 && l.ww4_off && !ctx->conv_naive &&
-        conv_wino4_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, ctx->wino_splitk ? &wino4_ks : nullptr) &&
-        (ctx->use_wino4 == 1 ||
-         (ctx->use_wino4 < 0 && wino4_auto(ctx->use_wino4, l.net == NET_POSE, l.k, l.cin_pad, l.cout_pad, Ho, Wo, B, wino4_ks, old_nt, wino_ks,
-                                           wino2_ks_probe(ctx, l, Ho, Wo, B, in_cs, out_cs, pool), ctx->two_streams_live)));
-    // round 6: the filled 3x3 launches with Cin >= 128 on the bf16 matrix pipe with split operands (conv_wino4s.hip), option "wino4_split"
-    int filled4s = 0;
-    const bool take4s = ctx->use_wino && ctx->use_wino4s && !f16 && l.ww4s_off && !ctx->conv_naive && l.k == 3 &&
-        conv_wino4s_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, &filled4s) &&
-        (ctx->use_wino4s == 1 || (take4 && wino4_ks <= 1 && filled4s));
-    if (take4s) {
-        ConvParams p;
-        p.in = in; p.wpk = ctx->blob + l.ww4s_off; p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = in_cs; p.Cout = l.cout_pad; p.out_cs = out_cs;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = l.relu; p.im2col = 0; p.ksplit = 1; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.nsub = 1;
-        if (ctx->w4_tail && conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
-            const size_t need = conv_wino4s_tail_floats();
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-            p.partial = ctx->col; p.partial_cap = ctx->col_floats;
-        }
-        {
-            ProfScope ps(ctx, l.name, pool ? "conv_wino4s_f4x4_3x3_bf16x3_pool" : "conv_wino4s_f4x4_3x3_bf16x3", flops, bytes);
-            const int lr = conv_wino4s_launch(p, pool, ctx->stream);
-            if (lr < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,3x3), split operands): launch refused");
-            if (lr == 1) ++ctx->conv_wino4s_tail_launches;
-        }
-        ++ctx->conv_wino4s_launches;
-        HIPCHK(ctx, hipGetLastError());
-        if (Ho_out) *Ho_out = pool ? Ho / 2 : Ho;
-        if (Wo_out) *Wo_out = pool ? Wo / 2 : Wo;
-        return 0;
-    }
-    const bool take2 = !take4 && ctx->use_wino && ctx->use_wino2 && !f16 && l.ww2_off && !ctx->conv_naive &&
-        conv_wino2_eligible(l.k, l.stride, l.cin_pad, l.cout_pad, Ho, Wo, B, in_cs, out_cs, pool, ctx->wino_splitk ? &wino2_ks : nullptr) &&
-        (ctx->use_wino2 == 1 || wino2_auto(l.k, l.cin_pad, l.cout_pad, Ho, Wo, B, old_nt, wino_ks, wino2_ks, ctx->two_streams_live));
-    if (take4 || take2) {
-        if (take4) wino2_ks = wino4_ks;          // (the block below serves both kernels: same parameters, same split / reduce protocol)
-        ConvParams p;
-        p.in = in; p.wpk = ctx->blob + (take4 ? l.ww4_off : l.ww2_off); p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = in_cs; p.Cout = l.cout_pad; p.out_cs = out_cs;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = l.relu; p.im2col = 0; p.ksplit = wino2_ks; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0;
-        p.nsub = l.k == 7 ? 9 : 1;
-        if (wino2_ks > 1) {
-            const size_t need = (size_t)wino2_ks * B * Ho * Wo * l.cout_pad;
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-            p.out = ctx->col; p.out_cs = l.cout_pad; p.cout_store = l.cout_pad;
-        } else if (take4 && l.k == 3 && ctx->w4_tail &&
-                   conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
-            // an under-filled last round of items runs as channel slices, one piece per CU (conv_wino4.hip, TAIL): scratch for the raw sums
-            const size_t need = conv_wino4_tail_floats();
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-            p.partial = ctx->col; p.partial_cap = ctx->col_floats;
-        }
-        {
-            const char* kn = take4 ? (l.k == 7 ? (wino2_ks > 1 ? "conv_wino4_f4x4_3x3_as7x7_splitk" : "conv_wino4_f4x4_3x3_as7x7")
-                                               : wino2_ks > 1 ? "conv_wino4_f4x4_3x3_splitk"
-                                               : pool ? "conv_wino4_f4x4_3x3_pool" : "conv_wino4_f4x4_3x3")
-                                    : (l.k == 7 ? (wino2_ks > 1 ? "conv_wino2_f2x2_3x3_as7x7_splitk" : "conv_wino2_f2x2_3x3_as7x7")
-                                               : wino2_ks > 1 ? "conv_wino2_f2x2_3x3_splitk" : pool ? "conv_wino2_f2x2_3x3_pool" : "conv_wino2_f2x2_3x3");
-            ProfScope ps(ctx, l.name, kn, flops, bytes);
-            // (the F(4x4,3x3) launchers answer 1 when the last round really ran as tail pieces: the counter below is the tests' proof)
-            const int lr = take4 ? conv_wino4_launch(p, wino2_ks > 1 ? 0 : pool, ctx->stream) : conv_wino2_launch(p, wino2_ks > 1 ? 0 : pool, ctx->stream);
-            if (lr < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (%s): launch refused", take4 ? "F(4x4,3x3)" : "2 workgroups per CU");
-            if (take4 && lr == 1) ++ctx->conv_wino4_tail_launches;
-        }
-        ++(take4 ? ctx->conv_wino4_launches : ctx->conv_wino2_launches);
-        if (wino2_ks > 1) {
-            ProfScope ps(ctx, l.name, pool ? "conv_splitk_reduce_pool" : "conv_splitk_reduce", 0.0, 4.0 * (wino2_ks + 1) * B * Ho * Wo * l.cout_pad);
-            if (pool)
-                conv_splitk_reduce_pool_launch(ctx->col, wino2_ks, B, Ho, Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs,
-                                               std::min(l.cout_pad, out_cs), ctx->stream);
-            else
-                conv_splitk_reduce_launch(ctx->col, wino2_ks, (long)B * Ho * Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs,
-                                          std::min(l.cout_pad, out_cs), ctx->stream);
-        }
-    } else if (old_nt) {
-        ConvParams p;
-        p.in = in; p.wpk = ctx->blob + l.ww_off; p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = in_cs; p.Cout = l.cout_pad; p.out_cs = out_cs;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl;
-        p.tiles_x = (Wo + 15) / 16; p.tiles_y = (Ho + 7) / 8;
-        p.act = l.relu; p.im2col = 0; p.ksplit = wino_ks; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0;
-        p.nsub = l.k == 7 ? 9 : 1;
-        if (wino_ks > 1) {       // under-filled chip: channel steps split over workgroups, raw partial sums, then one reduce
-            const size_t need = (size_t)wino_ks * B * Ho * Wo * l.cout_pad;
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-            p.out = ctx->col; p.out_cs = l.cout_pad; p.cout_store = l.cout_pad;
-        }
-        {
-            ProfScope ps(ctx, l.name, l.k == 7 ? (wino_ks > 1 ? "conv_wino_f2x2_3x3_as7x7_splitk" : "conv_wino_f2x2_3x3_as7x7")
-                                      : wino_ks > 1 ? "conv_wino_f2x2_3x3_splitk" : pool ? "conv_wino_f2x2_3x3_pool" : "conv_wino_f2x2_3x3", flops, bytes);
-            // split channel steps: raw partial sums at conv resolution, the pool (if any) happens in the reduce
-            if (conv_wino_launch(p, wino_ks > 1 ? 0 : pool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv: tensor exceeds 32-bit offsets");
-        }
-        if (wino_ks > 1) {
-            ProfScope ps(ctx, l.name, pool ? "conv_splitk_reduce_pool" : "conv_splitk_reduce", 0.0, 4.0 * (wino_ks + 1) * B * Ho * Wo * l.cout_pad);
-            if (pool)
-                conv_splitk_reduce_pool_launch(ctx->col, wino_ks, B, Ho, Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs,
-                                               std::min(l.cout_pad, out_cs), ctx->stream);
-            else
-                conv_splitk_reduce_launch(ctx->col, wino_ks, (long)B * Ho * Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs,
-                                          std::min(l.cout_pad, out_cs), ctx->stream);
-        }
+    const WinoPick wp = pick_wino(ctx, l, in_cs, out_cs, B, Ho, Wo, pool, f16);
+    if (wp.kind != WINO_NONE) {
+        CHK(run_wino(ctx, l, wp, conv_params(in, ctx->blob + wp.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo, l.cin_pad, in_cs, l.cout_pad,
+                                              out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu), pool, flops, bytes));
     } else if (l.mode == 1 && !pool && !out_f32 && ctx->use_first && !ctx->conv_naive &&
                conv_first_eligible(l.k, l.stride, l.cin, l.cout, B, H, W, out_cs, f16)) {
-        ConvParams p;
-        p.in = in; p.wpk = ctx->blob + l.w_off; p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = 3; p.in_cs = 3; p.Cout = 64; p.out_cs = out_cs; p.cout_store = 64;
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = l.relu; p.im2col = 1; p.ksplit = 1; p.partial = nullptr; p.f16 = f16; p.out_f32 = 0; p.nsub = 1;
-        // A COLD input image (the caller's device buffer, an upload: not written by the kernel in front of this one) costs this
-        // store-bound kernel a third of its rate -- its gathers run one tile ahead, an HBM miss takes longer than a tile (round 5: 3.5
-        // TB/s in the pipeline against 4.8 standalone and for PoseNet2D's freshly written crop).  Streaming the image once through the
-        // memory-side cache first (13 us for 39 MB) takes B = 32 at 320 x 320 from 0.253 to 0.175 ms (5.0 TB/s = 0.63 of the HBM spec).
-        const size_t img_bytes = (size_t)B * H * W * 12;
-        // The pass runs on the child context's stream BESIDE the convolution (it is ahead of the gathers after the first few tiles and
-        // needs 16 registers per wave next to the convolution's 3 x 160): its 13 us disappear; in this stream when there is no second one.
-        bool touch_beside = false;
-        if (ctx->d_keys && (ctx->first_touch == 1 || (ctx->first_touch < 0 && !ctx->trunk_input_hot && img_bytes >= (8u << 20) && img_bytes <= (128u << 20)))) {
-#ifndef HP3D_EMU
-            if (ctx->first_touch_beside && !ctx->use_graph && !ctx->shared_weights && !ctx->two_streams_live && kid_sync_state(ctx) == 0) {
-                hp3d_ctx* k = ctx->kid;
-                HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));          // (whatever produced the image on this stream comes first)
-                HIPCHK(ctx, hipStreamWaitEvent(k->stream, ctx->ev_fork, 0));
-                touch_launch(in, (size_t)B * H * W * 3, (float*)ctx->d_keys, k->stream);
-                HIPCHK(ctx, hipEventRecord(ctx->ev_join, k->stream));
-                touch_beside = true;
-            }
-#endif
-            if (!touch_beside) {
-                ProfScope pt(ctx, l.name, "conv_first_touch", 0.0, 0.0);
-                touch_launch(in, (size_t)B * H * W * 3, (float*)ctx->d_keys, ctx->stream);
-            }
-            ++ctx->first_touch_launches;
-        }
-        {
-            ProfScope ps(ctx, l.name, f16 ? "conv_first_3x3_c3_f16" : "conv_first_3x3_c3", flops, bytes);
-            conv_first_launch(p, ctx->stream, ctx->first_balanced);
-        }
-#ifndef HP3D_EMU
-        if (touch_beside) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // the call's completion covers the read pass
-#endif
-        ++ctx->conv_first_launches;
+        ConvParams p = conv_params(in, ctx->blob + l.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo, 3, 3, 64, out_cs, 64, pt, pl, l.relu);
+        p.im2col = 1; p.f16 = f16;
+        CHK(run_conv_first(ctx, l, p, flops, bytes));
     } else if (f16 && ctx->use_h16 && !ctx->conv_naive &&
                ((l.mode == 0 && l.k == 3) || (ctx->h16_k7k1 && ((l.k == 7 && (l.mode == 0 || l.mode == 2)) || (l.k == 1 && l.mode == 0)))) &&
                conv_h16_eligible(ctx->use_h16, l.k, l.stride, l.cin_pad16 / 2, l.cout_pad, Ho, Wo, B, out_f32, out_cs) &&
                ((uintptr_t)out & 15) == 0 && !(pool && ((Ho | Wo) & 1))) {
-        ConvParams p;
-        p.in = in; p.wpk = (const float*)(ctx->blob16 + l.w16_off); p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad16 / 2; p.in_cs = in_cs / 2; p.Cout = l.cout_pad; p.out_cs = out_cs;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = l.relu; p.im2col = 0; p.ksplit = 1; p.partial = nullptr; p.f16 = 1; p.out_f32 = 0; p.nsub = 1;
+        ConvParams p = conv_params(in, (const float*)(ctx->blob16 + l.w16_off), ctx->blob + l.b_off, out, B, H, W, Ho, Wo, l.cin_pad16 / 2, in_cs / 2,
+                                   l.cout_pad, out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu);
+        p.f16 = 1;
         ProfScope ps(ctx, l.name, l.k == 7 ? "conv_h16_7x7" : l.k == 1 ? "conv_h16_1x1" : pool ? "conv_h16_3x3_pool" : "conv_h16_3x3", flops, bytes);
         ++ctx->conv_h16_launches;
         if (conv_h16_launch(p, pool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_h16 launch failed for %s", l.name.c_str());
@@ -891,33 +876,19 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
         if (conv_mfma_plan(k, l.stride, Ho, Wo, cin_units, l.cout_pad, pool, B, &plan) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "no conv_mfma variant for %s (k=%d s=%d)", l.name.c_str(), k, l.stride);
         if (l.mode == 1 || (f16 && !out_f32)) plan.ksplit = 1;          // split-K partials are float32
-        if (plan.ksplit > 1) {
-            const size_t need = (size_t)plan.ksplit * B * Ho * Wo * l.cout_pad;
-            if (need > ctx->col_floats) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                CHK(dev_realloc(ctx, &ctx->col, need));
-                ctx->col_floats = need;
-            }
-        }
-        ConvParams p;
-        p.in = in; p.wpk = f16 ? (const float*)(ctx->blob16 + l.w16_off) : ctx->blob + l.w_off;
-        p.bias = ctx->blob + l.b_off; p.out = out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = cin_units; p.in_cs = (f16 && l.mode != 1) ? in_cs / 2 : in_cs; p.Cout = l.cout_pad; p.out_cs = out_cs;
+        if (plan.ksplit > 1) CHK(ensure_col(ctx, (size_t)plan.ksplit * B * Ho * Wo * l.cout_pad));
+        ConvParams p = conv_params(in, f16 ? (const float*)(ctx->blob16 + l.w16_off) : ctx->blob + l.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo,
+                                   cin_units, (f16 && l.mode != 1) ? in_cs / 2 : in_cs, l.cout_pad, out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu);
         p.f16 = f16; p.out_f32 = out_f32;
-        p.cout_store = std::min(l.cout_pad, out_cs);
-        p.pad_t = pt; p.pad_l = pl;
         p.tiles_x = (Wo + plan.tw - 1) / plan.tw; p.tiles_y = (Ho + plan.th - 1) / plan.th;
-        p.act = l.relu; p.im2col = (l.mode == 1);
+        p.im2col = (l.mode == 1);
         p.ksplit = plan.ksplit; p.partial = ctx->col;
         std::string kname = conv_mfma_variant_name(k, l.stride, pool, plan);
         if (f16) kname += "_f16";
         ProfScope ps(ctx, l.name, kname.c_str(), flops, bytes);
         if (conv_mfma_launch(p, k, l.stride, pool, plan, ctx->stream) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed for %s", l.name.c_str());
-        if (plan.ksplit > 1)
-            conv_splitk_reduce_launch(ctx->col, plan.ksplit, (long)B * Ho * Wo, l.cout_pad, p.bias, l.relu, out, out_cs,
-                                      p.cout_store, ctx->stream);
+        if (plan.ksplit > 1) splitk_reduce(ctx, l, plan.ksplit, B, Ho, Wo, pool, out, out_cs, false);      // (conv_mfma_plan splits no pooled layer)
     }
     HIPCHK(ctx, hipGetLastError());
     if (Ho_out) *Ho_out = pool ? Ho / 2 : Ho;
@@ -958,13 +929,9 @@ int run_fused12(hp3d_ctx* ctx, const ConvL& l1, const ConvL& l2, const float* im
         !l1.relu || !l2.relu || ((H | W) & 1) || ((uintptr_t)out & 15) ||
         !conv_h16_eligible(ctx->use_h16, l2.k, l2.stride, l2.cin_pad16 / 2, l2.cout_pad, H, W, B, 0, 64))
         return 0;
-    ConvParams p;
-    p.in = image; p.wpk = (const float*)(ctx->blob16 + l2.w16_off); p.bias = ctx->blob + l2.b_off; p.out = out;
+    ConvParams p = conv_params(image, (const float*)(ctx->blob16 + l2.w16_off), ctx->blob + l2.b_off, out, B, H, W, H, W, l2.cin_pad16 / 2, 3, 64, 64, 64, 1, 1, 1);
     p.wpk1 = ctx->blob + l1.w_off; p.bias1 = ctx->blob + l1.b_off;
-    p.B = B; p.H = H; p.W = W; p.Ho = H; p.Wo = W;
-    p.Cin = l2.cin_pad16 / 2; p.in_cs = 3; p.Cout = 64; p.out_cs = 64; p.cout_store = 64;
-    p.pad_t = 1; p.pad_l = 1; p.tiles_x = 0; p.tiles_y = 0;
-    p.act = 1; p.im2col = 1; p.ksplit = 1; p.partial = nullptr; p.f16 = 1; p.out_f32 = 0; p.nsub = 1;
+    p.im2col = 1; p.f16 = 1;
     const double px = (double)B * H * W;
     const double flops = 2.0 * 9 * (3.0 * 64 + 64.0 * 64) * px;
     const double bytes = px * 12 + 2.0 * (9 * 3 * 64 + 9 * 64 * 64) + 2.0 * px / 4 * 64;
@@ -1264,30 +1231,19 @@ int run_pose3d(hp3d_ctx* ctx, const float* sm32, const float* hs, int B, int var
         // leave most of the chip idle.  ViewpointNet runs on the child context's stream (own activations and partial sums, shared weights)
         // beside PosePrior on this one; the epilogue below waits for both.  Not while profiling per launch, replaying a graph, or when
         // this context is (or is busy with) the second stream of a two-stream call.
-        bool side = false;
-#ifndef HP3D_EMU
-        side = do_rot && ctx->lift_overlap && !ctx->profiling && !ctx->use_graph && !ctx->conv_naive && !ctx->shared_weights &&
-               !ctx->two_streams_live && kid_sync_state(ctx) == 0 && ensure_side_tower(ctx->kid, B) == 0;
+        const bool side = do_rot && ctx->lift_overlap && !ctx->profiling && !ctx->use_graph && !ctx->conv_naive && !ctx->shared_weights &&
+                          !ctx->two_streams_live && kid_sync_state(ctx) == 0 && ensure_side_tower(ctx->kid, B) == 0;
         if (side) {
             hp3d_ctx* k = ctx->kid;
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(ctx, hipStreamWaitEvent(k->stream, ctx->ev_fork, 0));
-            struct Join {       // recorded and waited for on every exit path (as in infer_full_chunked)
-                hp3d_ctx *p, *k;
-                ~Join() {
-                    if (hipEventRecord(p->ev_join, k->stream) == hipSuccess) (void)hipStreamWaitEvent(p->stream, p->ev_join, 0);
-                    else (void)hipStreamSynchronize(k->stream);
-                }
-            } join{ctx, k};
+            KidFork fork;
+            CHK(fork.fork(ctx));
             const int rc = run_viewpoint(k, sm32, hs, B, ctx->d_u);
             if (rc != 0) { set_error(ctx, k->err.c_str()); return rc; }
             if (beside_side && ctx->kp_up_side) { CHK((*beside_side)(k->stream)); beside_side = nullptr; }
             CHK(run_poseprior_can(ctx, sm32, hs, B, variant == HP3D_VARIANT_BOTTLENECK, ctx->d_can));
             if (beside) { CHK((*beside)(ctx->stream)); beside = nullptr; }
             ++ctx->lift_overlap_calls;
-        }
-#endif
-        if (!side) {
+        } else {
             CHK(run_poseprior_can(ctx, sm32, hs, B, variant == HP3D_VARIANT_BOTTLENECK, ctx->d_can));
             if (do_rot) CHK(run_viewpoint(ctx, sm32, hs, B, ctx->d_u));
         }
@@ -1506,8 +1462,7 @@ int kid_sync_state(hp3d_ctx* ctx) {
     }
     hp3d_ctx* k = ctx->kid;
     k->blob = ctx->blob; k->blob16 = ctx->blob16; k->nets = ctx->nets; k->prec = ctx->prec;
-    k->empty_fltmax = ctx->empty_fltmax; k->conv_naive = ctx->conv_naive; k->use_wino = ctx->use_wino;
-    k->use_first = ctx->use_first; k->first_touch = ctx->first_touch; k->first_balanced = ctx->first_balanced; k->use_wino2 = ctx->use_wino2; k->use_wino4 = ctx->use_wino4; k->fc_tail = ctx->fc_tail; k->tiny_gemm = ctx->tiny_gemm; k->use_wino4s = ctx->use_wino4s; k->w4_tail = ctx->w4_tail; k->use_wino7 = ctx->use_wino7; k->wino7_ksplit = ctx->wino7_ksplit; k->use_pw2 = ctx->use_pw2; k->use_lift_fused = ctx->use_lift_fused; k->use_h16 = ctx->use_h16; k->h16_k7k1 = ctx->h16_k7k1; k->fuse12 = ctx->fuse12; k->wino_splitk = ctx->wino_splitk; k->micro_batch = ctx->micro_batch; k->mask_grow = ctx->mask_grow;
+    static_cast<Options&>(*k) = *ctx;
     k->nstreams = 1; k->profiling = 0; k->use_graph = 0;
     return 0;
 #endif
@@ -1532,25 +1487,12 @@ int infer_full_chunked(hp3d_ctx* ctx, int B, int H, int W, const float* image, c
         (!image && !image_u8) || kid_sync_state(ctx) != 0)
         return infer_full_chunked1(ctx, B, H, W, image, hand_side, hand_scoremap, image_crop, scale_crop, center, kp_scoremap,
                                    coord3d, hand_mask, dev, image_u8, Hin, Win, kp_crop, kp_image);
-#ifndef HP3D_EMU
     hp3d_ctx* k = ctx->kid;
     const int b0 = (B + 1) / 2, b1 = B - b0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the child's stream starts after everything already queued on the parent's (inputs produced there) ...
-    HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(k->stream, ctx->ev_fork, 0));
+    KidFork fork;
+    CHK(fork.fork(ctx, true));
     auto off = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-    // Whatever happens below, the parent's stream must not run ahead of (and hp3d_sync / hp3d_dev_free / hp3d_destroy must
-    // cover) what was already enqueued on the child's stream: the join is recorded and waited for on EVERY exit path.
-    ctx->two_streams_live = k->two_streams_live = true;
-    struct Join {
-        hp3d_ctx *p, *k;
-        ~Join() {
-            p->two_streams_live = k->two_streams_live = false;
-            if (hipEventRecord(p->ev_join, k->stream) == hipSuccess) (void)hipStreamWaitEvent(p->stream, p->ev_join, 0);
-            else (void)hipStreamSynchronize(k->stream);
-        }
-    } join{ctx, k};
     // (host buffers: the child's pageable device->host copies block the host, so the two halves overlap on the `_dev`
     //  entry points only -- the ones bench.py and dist.py use)
     int rc = infer_full_chunked1(k, b1, H, W, image ? image + (size_t)b0 * H * W * 3 : nullptr, hand_side + (size_t)b0 * 2,
@@ -1562,15 +1504,12 @@ int infer_full_chunked(hp3d_ctx* ctx, int B, int H, int W, const float* image, c
     const int rc0 = rc != 0 ? rc : infer_full_chunked1(ctx, b0, H, W, image, hand_side, hand_scoremap, image_crop, scale_crop, center,
                                                        kp_scoremap, coord3d, hand_mask, dev, image_u8, Hin, Win, kp_crop, kp_image, true);
     if (rc0 != 0) return rc0;
-    // ... and the parent's stream continues only after the child's half is done (host buffers: wait for both here)
+    // (the parent's stream continues only after the child's half is done: the join; host buffers: wait for both here)
     if (!dev) {
         HIPCHK(ctx, hipStreamSynchronize(k->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     return 0;
-#else
-    return HP3D_ERR_UNSUPPORTED;
-#endif
 }
 
 int posenet_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image_crop, float* s0, float* s1, float* s2, bool dev) {
@@ -2383,12 +2322,8 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         std::vector<float> pk1(l1.b_off + 64);
         pack_conv(l1, w_hwio, bias, pk1.data());
         float* d_pk = S.upload(pk1.data(), pk1.size()); NN(ctx, d_pk);
-        ConvParams p;
-        p.in = d_x; p.wpk = d_pk; p.bias = d_pk + l1.b_off; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = 3; p.in_cs = 3; p.Cout = 64; p.out_cs = 64; p.cout_store = 64;
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = act; p.im2col = 1; p.ksplit = 1; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.nsub = 1;
+        ConvParams p = conv_params(d_x, d_pk, d_pk + l1.b_off, d_out, B, H, W, Ho, Wo, 3, 3, 64, 64, 64, pt, pl, act);
+        p.im2col = 1;
         conv_first_launch(p, ctx->stream, ctx->first_balanced);
         ++ctx->conv_first_launches;
         HIPCHK(ctx, hipGetLastError());
@@ -2405,12 +2340,8 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         wino7_pack_weights(w_hwio, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
         for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
         float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p;
-        p.in = d_xp; p.wpk = d_pk; p.bias = d_pk + wn; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = l.cin_pad; p.Cout = l.cout_pad; p.out_cs = Cout; p.cout_store = Cout;
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = act; p.im2col = 0; p.ksplit = op_ks7; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.nsub = 4;
+        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
+        p.ksplit = op_ks7; p.nsub = 4;
         float* d_part7 = nullptr;
         if (op_ks7 > 1) {          // under-filled launch: raw partial sums per channel split, then the deterministic reduce
             d_part7 = S.alloc<float>((size_t)op_ks7 * B * Ho * Wo * Cout); NN(ctx, d_part7);
@@ -2432,12 +2363,7 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         wino4s_pack_weights(w_hwio, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
         for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
         float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p;
-        p.in = d_xp; p.wpk = d_pk; p.bias = d_pk + wn; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = l.cin_pad; p.Cout = l.cout_pad; p.out_cs = Cout; p.cout_store = Cout;
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = act; p.im2col = 0; p.ksplit = 1; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0; p.nsub = 1;
+        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
         if (ctx->w4_tail && conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
             p.partial = S.alloc<float>(conv_wino4s_tail_floats()); NN(ctx, p.partial);
             p.partial_cap = conv_wino4s_tail_floats();
@@ -2462,13 +2388,8 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         else wino2_pack_weights(w_hwio, k, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
         for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
         float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p;
-        p.in = d_xp; p.wpk = d_pk; p.bias = d_pk + wn; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = l.cin_pad; p.Cout = l.cout_pad; p.out_cs = Cout; p.cout_store = Cout;
-        p.pad_t = pt; p.pad_l = pl; p.tiles_x = 0; p.tiles_y = 0;
-        p.act = act; p.im2col = 0; p.ksplit = op_ks2; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0;
-        p.nsub = k == 7 ? 9 : 1;
+        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
+        p.ksplit = op_ks2; p.nsub = k == 7 ? 9 : 1;
         float* d_part = nullptr;
         if (op_ks2 > 1) {
             d_part = S.alloc<float>((size_t)op_ks2 * B * Ho * Wo * Cout); NN(ctx, d_part);
@@ -2492,14 +2413,9 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         wino_pack_weights(w_hwio, k, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
         for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
         float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p;
-        p.in = d_xp; p.wpk = d_pk; p.bias = d_pk + wn; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = l.cin_pad; p.Cout = l.cout_pad; p.out_cs = Cout; p.cout_store = Cout;
-        p.pad_t = pt; p.pad_l = pl;
+        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
         p.tiles_x = (Wo + 15) / 16; p.tiles_y = (Ho + 7) / 8;
-        p.act = act; p.im2col = 0; p.ksplit = op_ks; p.partial = nullptr; p.f16 = 0; p.out_f32 = 0;
-        p.nsub = k == 7 ? 9 : 1;
+        p.ksplit = op_ks; p.nsub = k == 7 ? 9 : 1;
         float* d_part = nullptr;
         if (op_ks > 1) {
             d_part = S.alloc<float>((size_t)op_ks * B * Ho * Wo * Cout); NN(ctx, d_part);
@@ -2522,13 +2438,8 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "no conv_mfma variant for k=%d stride=%d pool=%d", k, stride, pool);
         float* d_part = nullptr;
         if (plan.ksplit > 1) { d_part = S.alloc<float>((size_t)plan.ksplit * B * Ho * Wo * l.cout_pad); NN(ctx, d_part); }
-        ConvParams p;
-        p.in = d_xp; p.wpk = d_pk; p.bias = d_pk + l.b_off; p.out = d_out;
-        p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-        p.Cin = l.cin_pad; p.in_cs = l.cin_pad; p.Cout = l.cout_pad; p.out_cs = Cout; p.cout_store = Cout;
-        p.pad_t = pt; p.pad_l = pl;
+        ConvParams p = conv_params(d_xp, d_pk, d_pk + l.b_off, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
         p.tiles_x = (Wo + plan.tw - 1) / plan.tw; p.tiles_y = (Ho + plan.th - 1) / plan.th;
-        p.act = act; p.im2col = 0; p.f16 = 0; p.out_f32 = 0;
         p.ksplit = plan.ksplit; p.partial = d_part;
         if (conv_mfma_launch(p, k, stride, pool, plan, ctx->stream) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed");
@@ -2687,29 +2598,34 @@ int hp3d_prof_get(hp3d_ctx* ctx, int i, char* name, int name_cap, char* kernel, 
 
 int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
     if (!ctx || !name || !value) return HP3D_ERR_ARG;
+    // {name, counter, + the child context's (every whole-path counter: the second stream's half ran there)}
+    static const struct { const char* name; long Counters::*member; bool with_kid; } table[] = {
+        {"graph_captures", &Counters::graph_captures, false},
+        {"graph_replays", &Counters::graph_replays, false},
+        {"lift_overlap_calls", &Counters::lift_overlap_calls, false},
+        {"mask_grow_global_launches", &Counters::mask_grow_global_launches, true},
+        {"conv_h16_launches", &Counters::conv_h16_launches, true},
+        {"conv_h16_first_resident_launches", &Counters::conv_h16_first_resident_launches, true},
+        {"first_touch_launches", &Counters::first_touch_launches, true},
+        {"conv_first_launches", &Counters::conv_first_launches, true},
+        {"lift_fused_launches", &Counters::lift_fused_launches, true},
+        {"conv_wino4_tail_launches", &Counters::conv_wino4_tail_launches, true},
+        {"conv_pw2_launches", &Counters::conv_pw2_launches, true},
+        {"conv_wino7_split_launches", &Counters::conv_wino7_split_launches, true},
+        {"conv_wino7_launches", &Counters::conv_wino7_launches, true},
+        {"fc_tail_launches", &Counters::fc_tail_launches, true},
+        {"conv_s2_gemm_launches", &Counters::conv_s2_gemm_launches, true},
+        {"conv_wino4s_launches", &Counters::conv_wino4s_launches, true},
+        {"conv_wino4s_tail_launches", &Counters::conv_wino4s_tail_launches, true},
+        {"conv_wino4_launches", &Counters::conv_wino4_launches, true},
+        {"conv_wino2_launches", &Counters::conv_wino2_launches, true},
+    };
     const std::string k(name);
-    if (k == "graph_captures") { *value = ctx->graph_captures; return 0; }
-    if (k == "graph_replays") { *value = ctx->graph_replays; return 0; }
-    if (k == "mask_grow_global_launches") { *value = ctx->mask_grow_global_launches + (ctx->kid ? ctx->kid->mask_grow_global_launches : 0); return 0; }
-    if (k == "conv_h16_launches") { *value = ctx->conv_h16_launches + (ctx->kid ? ctx->kid->conv_h16_launches : 0); return 0; }
-    if (k == "conv_h16_first_resident_launches") { *value = ctx->conv_h16_first_resident_launches + (ctx->kid ? ctx->kid->conv_h16_first_resident_launches : 0); return 0; }
-    if (k == "first_touch_launches") { *value = ctx->first_touch_launches + (ctx->kid ? ctx->kid->first_touch_launches : 0); return 0; }
-    if (k == "conv_first_launches") { *value = ctx->conv_first_launches + (ctx->kid ? ctx->kid->conv_first_launches : 0); return 0; }
-    if (k == "lift_overlap_calls") { *value = ctx->lift_overlap_calls; return 0; }
-    if (k == "lift_fused_launches") { *value = ctx->lift_fused_launches + (ctx->kid ? ctx->kid->lift_fused_launches : 0); return 0; }
-    if (k == "conv_wino4_tail_launches") { *value = ctx->conv_wino4_tail_launches + (ctx->kid ? ctx->kid->conv_wino4_tail_launches : 0); return 0; }
-    if (k == "conv_pw2_launches") { *value = ctx->conv_pw2_launches + (ctx->kid ? ctx->kid->conv_pw2_launches : 0); return 0; }
-    if (k == "conv_wino7_split_launches") { *value = ctx->conv_wino7_split_launches + (ctx->kid ? ctx->kid->conv_wino7_split_launches : 0); return 0; }
-    if (k == "conv_wino7_launches") { *value = ctx->conv_wino7_launches + (ctx->kid ? ctx->kid->conv_wino7_launches : 0); return 0; }
+    for (const auto& c : table)
+        if (k == c.name) { *value = ctx->*c.member + (c.with_kid && ctx->kid ? ctx->kid->*c.member : 0); return 0; }
 #ifdef HP3D_EMU
     if (k == "emu_soff_overreads") { *value = (long)hp3d_emu_soff_overreads; return 0; }     // interpreter only: 16-byte loads that left their buffer through the scalar offset
 #endif
-    if (k == "fc_tail_launches") { *value = ctx->fc_tail_launches + (ctx->kid ? ctx->kid->fc_tail_launches : 0); return 0; }
-    if (k == "conv_s2_gemm_launches") { *value = ctx->conv_s2_gemm_launches + (ctx->kid ? ctx->kid->conv_s2_gemm_launches : 0); return 0; }
-    if (k == "conv_wino4s_launches") { *value = ctx->conv_wino4s_launches + (ctx->kid ? ctx->kid->conv_wino4s_launches : 0); return 0; }
-    if (k == "conv_wino4s_tail_launches") { *value = ctx->conv_wino4s_tail_launches + (ctx->kid ? ctx->kid->conv_wino4s_tail_launches : 0); return 0; }
-    if (k == "conv_wino4_launches") { *value = ctx->conv_wino4_launches + (ctx->kid ? ctx->kid->conv_wino4_launches : 0); return 0; }
-    if (k == "conv_wino2_launches") { *value = ctx->conv_wino2_launches + (ctx->kid ? ctx->kid->conv_wino2_launches : 0); return 0; }
     if (k == "comm_ranks") { *value = comm_ranks(ctx); return 0; }
     HP3D_FAIL(ctx, HP3D_ERR_ARG, "unknown counter %s", name);
 }

@@ -1421,8 +1421,24 @@ def test_two_streams_equal_one_stream(net, synth_weights):
         assert np.array_equal(eng.to_host(d_c, (5, 21, 3)), two['coord3d'])
         for buf in (d_img, d_hs, d_c):
             buf.free()
+        # a plan option set on the parent holds for the second stream's half as well (the child context copies the whole option
+        # record): F(4x4,3x3) off -> neither half launches it; conv_impl=direct -> neither half's conv1_1 runs on conv_first.hip
+        eng.set_option('wino4', '0')
+        n4 = eng.counter('conv_wino4_launches')
+        eng.infer_full(img, hs, want_mask=True)
+        assert eng.counter('conv_wino4_launches') == n4
+        eng.set_option('wino4', 'auto')
+        n1 = eng.counter('conv_first_launches')
+        eng.infer_full(img, hs, want_mask=True)
+        assert eng.counter('conv_first_launches') > n1
+        eng.set_option('conv_impl', 'direct')
+        n1 = eng.counter('conv_first_launches')
+        eng.infer_full(img, hs, want_mask=True)
+        assert eng.counter('conv_first_launches') == n1
     finally:
         eng.set_option('streams', 'auto')
+        eng.set_option('wino4', 'auto')
+        eng.set_option('conv_impl', 'mfma')
 
 
 def test_stream_policy_follows_the_batch_size(net, synth_weights):
