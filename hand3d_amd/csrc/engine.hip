@@ -288,6 +288,9 @@ struct Counters {
     long conv_wino4_tail_launches = 0;
     long conv_wino4_launches = 0;                   // layers that went to conv_wino4.hip
     long conv_wino2_launches = 0;                   // layers that went to conv_wino2.hip
+    long conv_wino_launches = 0;                    // layers that went to conv_wino.hip
+    long conv_mfma_launches = 0;                    // layers that went to the general direct kernel (conv_mfma.hip, f32 and f16)
+    long conv_splitk_reduce_launches = 0;           // channel-split reduces (conv_splitk_reduce*_launch)
     long mask_grow_global_launches = 0;             // mask growths on the global-scratch kernel
 };
 
@@ -693,6 +696,7 @@ int ensure_col(hp3d_ctx* ctx, size_t floats) {
 // max-pool) -> out.  profile = false: no profile row (conv_mfma's reduce never had one).
 void splitk_reduce(hp3d_ctx* ctx, const ConvL& l, int ks, int B, int Ho, int Wo, int pool, float* out, int out_cs, bool profile = true) {
     ProfScope ps(ctx, l.name, !profile ? nullptr : pool ? "conv_splitk_reduce_pool" : "conv_splitk_reduce", 0.0, 4.0 * (ks + 1) * B * Ho * Wo * l.cout_pad);
+    ++ctx->conv_splitk_reduce_launches;
     if (pool)
         conv_splitk_reduce_pool_launch(ctx->col, ks, B, Ho, Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
     else
@@ -790,6 +794,7 @@ int run_wino(hp3d_ctx* ctx, const ConvL& l, const WinoPick& w, ConvParams p, int
             break;
         default:
             if (conv_wino_launch(p, lpool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv: tensor exceeds 32-bit offsets");
+            ++ctx->conv_wino_launches;
         }
     }
     if (w.ks > 1) splitk_reduce(ctx, l, w.ks, B, Ho, Wo, pool, out, out_cs);
@@ -888,6 +893,7 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
         ProfScope ps(ctx, l.name, kname.c_str(), flops, bytes);
         if (conv_mfma_launch(p, k, l.stride, pool, plan, ctx->stream) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed for %s", l.name.c_str());
+        ++ctx->conv_mfma_launches;
         if (plan.ksplit > 1) splitk_reduce(ctx, l, plan.ksplit, B, Ho, Wo, pool, out, out_cs, false);      // (conv_mfma_plan splits no pooled layer)
     }
     HIPCHK(ctx, hipGetLastError());
@@ -2348,7 +2354,10 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
             p.out = d_part7;
         }
         if (conv_wino7_launch(p, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,4x4)): launch refused");
-        if (op_ks7 > 1) conv_splitk_reduce_launch(d_part7, op_ks7, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
+        if (op_ks7 > 1) {
+            conv_splitk_reduce_launch(d_part7, op_ks7, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
+            ++ctx->conv_splitk_reduce_launches;
+        }
         ++ctx->conv_wino7_launches;
         ctx->conv_wino7_split_launches += op_ks7 > 1;
         HIPCHK(ctx, hipGetLastError());
@@ -2407,6 +2416,7 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
             conv_splitk_reduce_pool_launch(d_part, op_ks2, B, Ho, Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
         else if (op_ks2 > 1)
             conv_splitk_reduce_launch(d_part, op_ks2, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
+        ctx->conv_splitk_reduce_launches += op_ks2 > 1;
     } else if (ctx->use_wino && !ctx->conv_naive && conv_wino_eligible(ctx->use_wino, k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, pool, ctx->wino_splitk ? &op_ks : nullptr) && Cout % 64 == 0) {
         const size_t wn = wino_packed_floats(k, l.cin_pad, l.cout_pad);
         std::vector<float> pw(wn + l.cout_pad, 0.f);
@@ -2422,10 +2432,12 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
             p.out = d_part;
         }
         if (conv_wino_launch(p, op_ks > 1 ? 0 : pool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv: tensor exceeds 32-bit offsets");
+        ++ctx->conv_wino_launches;
         if (op_ks > 1 && pool)
             conv_splitk_reduce_pool_launch(d_part, op_ks, B, Ho, Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
         else if (op_ks > 1)
             conv_splitk_reduce_launch(d_part, op_ks, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
+        ctx->conv_splitk_reduce_launches += op_ks > 1;
     } else if (ctx->conv_naive) {
         if (pool) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "naive conv has no fused pool");
         float* d_w = S.upload(w_hwio, (size_t)k * k * Cin * Cout); NN(ctx, d_w);
@@ -2443,9 +2455,11 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
         p.ksplit = plan.ksplit; p.partial = d_part;
         if (conv_mfma_launch(p, k, stride, pool, plan, ctx->stream) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed");
+        ++ctx->conv_mfma_launches;
         if (plan.ksplit > 1)
             conv_splitk_reduce_launch(d_part, plan.ksplit, (long)B * Ho * Wo, l.cout_pad, p.bias, act, d_out, Cout, Cout,
                                       ctx->stream);
+        ctx->conv_splitk_reduce_launches += plan.ksplit > 1;
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)B * Hs * Ws * Cout, hipMemcpyDeviceToHost, ctx->stream));
@@ -2619,6 +2633,9 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"conv_wino4s_tail_launches", &Counters::conv_wino4s_tail_launches, true},
         {"conv_wino4_launches", &Counters::conv_wino4_launches, true},
         {"conv_wino2_launches", &Counters::conv_wino2_launches, true},
+        {"conv_wino_launches", &Counters::conv_wino_launches, true},
+        {"conv_mfma_launches", &Counters::conv_mfma_launches, true},
+        {"conv_splitk_reduce_launches", &Counters::conv_splitk_reduce_launches, true},
     };
     const std::string k(name);
     for (const auto& c : table)

@@ -321,6 +321,9 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "first_touch_launches" = read passes in front of conv1_1 (option "first_touch");
  * "mask_grow_global_launches" = mask growths (one launch per call or chunk, all its images) on the global-scratch kernel (option "mask_grow");
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
+ * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
+ * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
+ * "conv_splitk_reduce_launches" = channel-split reduces behind a conv_mfma / Winograd launch (whole path and hp3d_conv2d);
  * "lift_overlap_calls" = lifting stages that ran their two towers on two streams (option "lift_overlap");
  * "lift_fused_launches" = lifting stages that ran as the one fused launch (option "lift_fused"); "comm_ranks" = ranks of the live RCCL communicator as RCCL itself
  * reports them (ncclCommCount), 0 without one -- bench.py prints it so that a multi-GPU line proves its own world size.

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from hand3d_amd import synth
+from oracle import conv_exact as X
 from oracle import general as G
 from oracle import nets as N
 from oracle import tf_ops as T
@@ -87,7 +88,9 @@ def test_conv_winograd_vs_oracle(gpu_engine, case):
     r = _conv_ref(x, w, b, 1, True, pool)
     gpu_engine.set_option('conv_impl', 'winograd')
     try:
+        n0 = gpu_engine.counter('conv_wino_launches')
         y = gpu_engine.conv2d(x, w, b, 1, True, bool(pool))
+        assert gpu_engine.counter('conv_wino_launches') == n0 + 1, "the Winograd kernel did not run"
     finally:
         gpu_engine.set_option('conv_impl', 'mfma')
     gpu_engine.set_option('conv_impl', 'direct')
@@ -98,7 +101,6 @@ def test_conv_winograd_vs_oracle(gpu_engine, case):
     err, errd = np.abs(y - r).max(), np.abs(yd - r).max()
     print("winograd %s max|err| %.3e (direct %.3e)" % (case, err, errd))
     assert y.shape == r.shape and err < 5e-5
-    assert not np.array_equal(y, yd), "the Winograd kernel did not run"
 
 
 W2_CASES = WINO_CASES + [(1, 32, 32, 256, 256, 0), (1, 32, 32, 512, 512, 0), (1, 128, 128, 64, 64, 1), (32, 160, 160, 64, 128, 0),
@@ -115,7 +117,7 @@ def test_conv_winograd_two_workgroups_per_cu_vs_oracle(gpu_engine, case):
     x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
     w = (rng.standard_normal((3, 3, Cin, Cout)) / np.sqrt(9 * Cin)).astype(np.float32)
     b = rng.standard_normal(Cout).astype(np.float32)
-    big = B * H * W * Cout > 3e7          # the NumPy oracle needs a minute there: compare with conv_wino.hip instead (itself oracle-checked)
+    big = B * H * W * Cout > 3e7          # the NumPy oracle needs a minute there: the float64 torch reference instead
     gpu_engine.set_option('wino2', '1')
     try:
         n0 = gpu_engine.counter('conv_wino2_launches')
@@ -126,16 +128,7 @@ def test_conv_winograd_two_workgroups_per_cu_vs_oracle(gpu_engine, case):
             assert np.array_equal(y, y2), "not deterministic"
     finally:
         gpu_engine.set_option('wino2', 'auto')
-    if big:
-        gpu_engine.set_option('wino2', '0')
-        gpu_engine.set_option('conv_impl', 'winograd')
-        try:
-            r = gpu_engine.conv2d(x, w, b, 1, True, bool(pool))
-        finally:
-            gpu_engine.set_option('conv_impl', 'mfma')
-            gpu_engine.set_option('wino2', 'auto')
-    else:
-        r = _conv_ref(x, w, b, 1, True, pool)
+    r = X.conv_ref_f64(x, w, b, 1, True, bool(pool)) if big else _conv_ref(x, w, b, 1, True, pool)
     err = np.abs(y - r).max()
     print("conv_wino2 %s max|err| %.3e" % (case, err))
     assert y.shape == r.shape and err < 5e-5
@@ -157,16 +150,7 @@ def test_conv_winograd_two_workgroups_per_cu_7x7(gpu_engine, case):
         assert gpu_engine.counter('conv_wino2_launches') == n0 + 1
     finally:
         gpu_engine.set_option('wino2', 'auto')
-    if B <= 4:
-        r = _conv_ref(x, w, b, 1, True, 0)
-    else:
-        gpu_engine.set_option('wino2', '0')
-        gpu_engine.set_option('conv_impl', 'winograd')
-        try:
-            r = gpu_engine.conv2d(x, w, b, 1, True, False)
-        finally:
-            gpu_engine.set_option('conv_impl', 'mfma')
-            gpu_engine.set_option('wino2', 'auto')
+    r = _conv_ref(x, w, b, 1, True, 0) if B <= 4 else X.conv_ref_f64(x, w, b, 1, True, False)
     err = np.abs(y - r).max()
     print("conv_wino2 7x7 %s max|err| %.3e" % (case, err))
     assert err < 5e-5
@@ -179,8 +163,7 @@ def test_conv_winograd_f4x4_tail_pieces(gpu_engine, case):
     layers at B = 32 are 800 items on 256 CUs -- shares that round's item-steps out in equal runs, one per CU (a run may cross from one
     item into the next), and wino4_tail_reduce adds an item's raw pieces in step order.  Shapes: a quarter round left, an eighth, a
     pooled layer, more than half a round with ragged tiles, less than one round in all.  Against the same kernel with the option off
-    (only the tail items may differ, by summation order) and against conv_wino.hip (F(2x2,3x3), itself oracle-checked); deterministic;
-    the counter proves the path ran."""
+    (only the tail items may differ, by summation order) and against the float64 reference; deterministic; the counter proves the path ran."""
     B, H, W, Cin, Cout, pool = case
     rng = np.random.default_rng(sum(case) + 21)
     x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
@@ -199,16 +182,11 @@ def test_conv_winograd_f4x4_tail_pieces(gpu_engine, case):
     finally:
         gpu_engine.set_option('wino4_tail', '1')
         gpu_engine.set_option('wino_splitk', '1')
-        gpu_engine.set_option('wino4', '0')
-    gpu_engine.set_option('conv_impl', 'winograd')
-    try:
-        r = gpu_engine.conv2d(x, w, b, 1, True, bool(pool))
-    finally:
-        gpu_engine.set_option('conv_impl', 'mfma')
         gpu_engine.set_option('wino4', 'auto')
+    r = X.conv_ref_f64(x, w, b, 1, True, bool(pool))
     d = np.abs(y - y0)
     frac = float((d > 0).mean())
-    print("tail pieces %s: vs unsplit %.2e on %.1f %% of the outputs, vs F(2x2,3x3) %.2e" % (case, d.max(), 100 * frac, np.abs(y - r).max()))
+    print("tail pieces %s: vs unsplit %.2e on %.1f %% of the outputs, vs float64 %.2e" % (case, d.max(), 100 * frac, np.abs(y - r).max()))
     assert y.shape == r.shape and d.max() < 1e-4 and 0 < frac < (1.01 if B * H < 200 else 0.5) and np.abs(y - r).max() < 2e-4
 
 
@@ -231,7 +209,7 @@ def test_conv_winograd_f4x4_vs_oracle(gpu_engine, case):
     x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
     w = (rng.standard_normal((k, k, Cin, Cout)) / np.sqrt(k * k * Cin)).astype(np.float32)
     b = rng.standard_normal(Cout).astype(np.float32)
-    big = B * H * W * Cout * k * k > 2.5e8          # the NumPy oracle needs minutes there: compare with conv_wino.hip instead (itself oracle-checked)
+    big = B * H * W * Cout * k * k > 2.5e8          # the NumPy oracle needs minutes there: the float64 torch reference instead
     gpu_engine.set_option('wino4', '1')
     try:
         n0 = gpu_engine.counter('conv_wino4_launches')
@@ -241,16 +219,7 @@ def test_conv_winograd_f4x4_vs_oracle(gpu_engine, case):
             assert np.array_equal(y, gpu_engine.conv2d(x, w, b, 1, True, bool(pool))), "not deterministic"
     finally:
         gpu_engine.set_option('wino4', 'auto')
-    if big:
-        gpu_engine.set_option('wino4', '0')
-        gpu_engine.set_option('conv_impl', 'winograd')
-        try:
-            r = gpu_engine.conv2d(x, w, b, 1, True, bool(pool))
-        finally:
-            gpu_engine.set_option('conv_impl', 'mfma')
-            gpu_engine.set_option('wino4', 'auto')
-    else:
-        r = _conv_ref(x, w, b, 1, True, pool)
+    r = X.conv_ref_f64(x, w, b, 1, True, bool(pool)) if big else _conv_ref(x, w, b, 1, True, pool)
     err = np.abs(y - r).max()
     print("conv_wino4 %s max|err| %.3e" % (case, err))
     assert y.shape == r.shape and err < 2e-4
@@ -272,7 +241,7 @@ def test_conv_winograd_f4x4_split_operands_vs_oracle(gpu_engine, case):
     x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
     w = (rng.standard_normal((3, 3, Cin, Cout)) / np.sqrt(9 * Cin)).astype(np.float32)
     b = rng.standard_normal(Cout).astype(np.float32)
-    big = B * H * W * Cout * 9 > 2.5e8          # the NumPy oracle needs minutes there: compare with conv_wino.hip instead (itself oracle-checked)
+    big = B * H * W * Cout * 9 > 2.5e8          # the NumPy oracle needs minutes there: the float64 torch reference instead
     gpu_engine.set_option('wino4_split', '1')
     try:
         n0 = gpu_engine.counter('conv_wino4s_launches')
@@ -282,16 +251,7 @@ def test_conv_winograd_f4x4_split_operands_vs_oracle(gpu_engine, case):
             assert np.array_equal(y, gpu_engine.conv2d(x, w, b, 1, True, bool(pool))), "not deterministic"
     finally:
         gpu_engine.set_option('wino4_split', '0')
-    if big:
-        gpu_engine.set_option('wino4', '0')
-        gpu_engine.set_option('conv_impl', 'winograd')
-        try:
-            r = gpu_engine.conv2d(x, w, b, 1, True, bool(pool))
-        finally:
-            gpu_engine.set_option('conv_impl', 'mfma')
-            gpu_engine.set_option('wino4', 'auto')
-    else:
-        r = _conv_ref(x, w, b, 1, True, pool)
+    r = X.conv_ref_f64(x, w, b, 1, True, bool(pool)) if big else _conv_ref(x, w, b, 1, True, pool)
     err = np.abs(y - r).max()
     print("conv_wino4s %s max|err| %.3e" % (case, err))
     assert y.shape == r.shape and err < 2e-4
