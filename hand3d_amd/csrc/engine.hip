@@ -1,6 +1,9 @@
 // engine.hip -- context, weight packing, stream-ordered executor and the C-ABI of libhp3d.so.
 // Host code only (the kernels live in conv_mfma.hip / glue.hip).  See include/hp3d.h for the
 // reference interfaces each entry point replaces.
+// One convolution path: reserve_conv lays a layer's filter sections out, pack_layer fills them, run_conv picks the kernel and launches
+// it.  The networks' layers live in the context's blob (Tables); hp3d_conv2d describes its one layer, packs it into a scratch blob and
+// calls the same run_conv -- of its own it only chooses which sections that layer has.
 #include "hp3d_common.h"
 #include "lift_fused.h"
 #include "../../include/hp3d.h"
@@ -74,6 +77,39 @@ struct FcL {
 
 int pad32(int c) { return (c + 31) / 32 * 32; }
 
+// The optional sections of a layer's packed filters.  Which of them a layer carries is its owner's choice (Tables::add_conv for the
+// networks, hp3d_conv2d for its one layer); how large and how aligned each one is, is reserve_conv's alone.
+enum { SEC_WINO = 1, SEC_WINO2 = 2, SEC_WINO4 = 4, SEC_WINO7 = 8, SEC_WINO4S = 16, SEC_RAW = 32, SEC_HWIO = 64, SEC_F16 = 128 };
+
+// Lays the direct filters, the bias and the sections `secs` of layer l (k, cin, cout, mode, ek, cin_pad, cout_pad set) out behind
+// `floats`, the half-precision filters behind `halves`.  An absent section keeps offset 0: behind the direct filters no section starts there.
+void reserve_conv(ConvL& l, int secs, size_t& floats, size_t& halves) {
+    auto take = [&](size_t n, bool align16 = false) {
+        if (align16) floats = (floats + 3) / 4 * 4;
+        const size_t off = floats;
+        floats += n;
+        return off;
+    };
+    l.w_off = take((size_t)l.ek * l.ek * l.cin_pad * l.cout_pad);
+    l.b_off = take(l.cout_pad);
+    // Winograd F(2x2,3x3) copies (16 planes; a 7x7 filter as nine 3x3 blocks along the channel axis)
+    if (secs & SEC_WINO) l.ww_off = take(wino_packed_floats(l.k, l.cin_pad, l.cout_pad));
+    if (secs & SEC_WINO2) l.ww2_off = take(wino_packed_floats(l.k, l.cin_pad, l.cout_pad));
+    if (secs & SEC_WINO4) l.ww4_off = take(wino4_packed_floats(l.k, l.cin_pad, l.cout_pad));
+    if (secs & SEC_WINO7) l.ww7_off = take(wino7_packed_floats(l.cin_pad, l.cout_pad));
+    if (secs & SEC_WINO4S) l.ww4s_off = take((wino4s_packed_bytes(l.cin_pad, l.cout_pad) + 15) / 16 * 4, true);
+    if (secs & SEC_RAW) {
+        l.cin4 = (l.cin + 15) / 16 * 16;          // four waves x whole channel quads
+        l.raw_off = take((size_t)9 * l.cin4 * ((l.cout + 63) / 64 * 64));
+    }
+    if (secs & SEC_HWIO) l.hwio_off = take((size_t)9 * l.cin * l.cout, true);
+    if (secs & SEC_F16) {
+        l.cin_pad16 = (l.mode == 1) ? 64 : (l.mode == 2) ? 192 : (l.cin + 63) / 64 * 64;
+        l.w16_off = halves;
+        halves += (size_t)l.ek * l.ek * l.cin_pad16 * l.cout_pad;
+    }
+}
+
 struct Tables {
     std::vector<ConvL> conv;
     std::vector<FcL> fc;
@@ -88,45 +124,16 @@ struct Tables {
         l.ek = (l.mode == 1) ? 1 : k;
         l.cin_pad = (l.mode == 1) ? 32 : (l.mode == 2) ? 160 : pad32(cin);
         l.cout_pad = pad32(cout);
-        l.w_off = blob_floats;
-        blob_floats += (size_t)l.ek * l.ek * l.cin_pad * l.cout_pad;
-        l.b_off = blob_floats;
-        blob_floats += l.cout_pad;
-        // Winograd F(2x2,3x3) copy (16 planes; a 7x7 filter as nine 3x3 blocks along the channel axis)
+        const bool trunk = net == NET_SEG || net == NET_POSE;
+        int secs = 0;
         if (stride == 1 && cout % 64 == 0 && ((k == 3 && l.mode == 0) || (k == 7 && (l.mode == 0 || l.mode == 2)))) {
-            l.ww_off = blob_floats;
-            blob_floats += wino_packed_floats(k, l.cin_pad, l.cout_pad);
-            l.ww2_off = blob_floats;
-            blob_floats += wino_packed_floats(k, l.cin_pad, l.cout_pad);
-            if (net == NET_SEG || net == NET_POSE) {
-                l.ww4_off = blob_floats;
-                blob_floats += wino4_packed_floats(k, l.cin_pad, l.cout_pad);
-                if (k == 7) {
-                    l.ww7_off = blob_floats;
-                    blob_floats += wino7_packed_floats(l.cin_pad, l.cout_pad);
-                }
-                if (k == 3 && l.mode == 0 && l.cin_pad >= 128 && l.cin_pad % 16 == 0) {
-                    blob_floats = (blob_floats + 3) / 4 * 4;
-                    l.ww4s_off = blob_floats;
-                    blob_floats += (wino4s_packed_bytes(l.cin_pad, l.cout_pad) + 15) / 16 * 4;
-                }
-            }
+            secs |= SEC_WINO | SEC_WINO2;
+            if (trunk) secs |= SEC_WINO4 | (k == 7 ? SEC_WINO7 : 0) | (k == 3 && l.mode == 0 && l.cin_pad >= 128 && l.cin_pad % 16 == 0 ? SEC_WINO4S : 0);
         }
-        if (net == NET_PRIOR || net == NET_VP) {
-            l.cin4 = (cin + 15) / 16 * 16;          // four waves x whole channel quads
-            l.raw_off = blob_floats;
-            blob_floats += (size_t)9 * l.cin4 * ((cout + 63) / 64 * 64);
-        }
-        if (net == NET_VP && stride == 2 && k == 3 && cin >= 256) {          // (ViewpointNet/conv_vp_2_2: 47 -> 39 us; PosePrior's 128-channel twin measured slower this way)
-            blob_floats = (blob_floats + 3) / 4 * 4;
-            l.hwio_off = blob_floats;
-            blob_floats += (size_t)9 * cin * cout;
-        }
-        if (net == NET_SEG || net == NET_POSE) {     // half-precision copy for hp3d_finalize_weights(dtype=1)
-            l.cin_pad16 = (l.mode == 1) ? 64 : (l.mode == 2) ? 192 : (cin + 63) / 64 * 64;
-            l.w16_off = blob16_halves;
-            blob16_halves += (size_t)l.ek * l.ek * l.cin_pad16 * l.cout_pad;
-        }
+        if (net == NET_PRIOR || net == NET_VP) secs |= SEC_RAW;         // lift_fused.hip's weight streams
+        if (net == NET_VP && stride == 2 && k == 3 && cin >= 256) secs |= SEC_HWIO;         // (ViewpointNet/conv_vp_2_2: 47 -> 39 us; PosePrior's 128-channel twin measured slower this way)
+        if (trunk) secs |= SEC_F16;                 // half-precision copy for hp3d_finalize_weights(dtype=1)
+        reserve_conv(l, secs, blob_floats, blob16_halves);
         conv_idx[l.name] = (int)conv.size();
         conv.push_back(l);
     }
@@ -434,6 +441,30 @@ void pack_conv(const ConvL& l, const float* w, const float* b, float* blob) {
         }
 }
 
+// Every float32 section layer l has reserved (reserve_conv), from its HWIO filter w and bias b.
+void pack_layer(const ConvL& l, const float* w, const float* b, float* blob) {
+    pack_conv(l, w, b, blob);
+    if (l.raw_off)          // lift_fused.hip: [cout block of 64][cin4][tap][64], zero rows / columns as padding
+        for (int t = 0; t < 9; ++t)
+            for (int c = 0; c < l.cin; ++c)
+                for (int co = 0; co < l.cout; ++co)
+                    blob[l.raw_off + (((size_t)(co >> 6) * l.cin4 + c) * 9 + t) * 64 + (co & 63)] = w[((size_t)t * l.cin + c) * l.cout + co];
+    if (l.hwio_off) memcpy(blob + l.hwio_off, w, sizeof(float) * (size_t)9 * l.cin * l.cout);
+    if (!(l.ww_off || l.ww2_off || l.ww4_off || l.ww7_off || l.ww4s_off)) return;
+    // U = G g G^T in the Winograd kernels' fragment orders
+    std::vector<int> cmap(l.cin_pad, -1);
+    for (int e = 0; e < l.cin_pad; ++e) {
+        if (l.mode == 0) cmap[e] = e < l.cin ? e : -1;
+        else if (e < 128) cmap[e] = 21 + e;            // concat buffer [encoding | scoremap | 0] vs reference [scoremap, encoding]
+        else if (e < 149) cmap[e] = e - 128;
+    }
+    if (l.ww_off) wino_pack_weights(w, l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), blob + l.ww_off);
+    if (l.ww2_off) wino2_pack_weights(w, l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), blob + l.ww2_off);
+    if (l.ww4_off) wino4_pack_weights(w, l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), blob + l.ww4_off);
+    if (l.ww7_off) wino7_pack_weights(w, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), blob + l.ww7_off);
+    if (l.ww4s_off) wino4s_pack_weights(w, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), blob + l.ww4s_off);
+}
+
 // half-precision packing: wpk16[tap][Cin/16][Cout/32][h][n][8] = W[tap][ref_channel(16*kb + 8*h + e)][32*co32 + n]
 void pack_conv16(const ConvL& l, const float* w, hp3d_f16* blob16) {
     hp3d_f16* wp = blob16 + l.w16_off;
@@ -694,13 +725,13 @@ int ensure_col(hp3d_ctx* ctx, size_t floats) {
 
 // The reduce behind a channel-split launch: ctx->col = [ks][B*Ho*Wo][cout_pad] raw sums -> bias + activation (+ the layer's 2x2
 // max-pool) -> out.  profile = false: no profile row (conv_mfma's reduce never had one).
-void splitk_reduce(hp3d_ctx* ctx, const ConvL& l, int ks, int B, int Ho, int Wo, int pool, float* out, int out_cs, bool profile = true) {
+void splitk_reduce(hp3d_ctx* ctx, const ConvL& l, const float* bias, int ks, int B, int Ho, int Wo, int pool, float* out, int out_cs, bool profile = true) {
     ProfScope ps(ctx, l.name, !profile ? nullptr : pool ? "conv_splitk_reduce_pool" : "conv_splitk_reduce", 0.0, 4.0 * (ks + 1) * B * Ho * Wo * l.cout_pad);
     ++ctx->conv_splitk_reduce_launches;
     if (pool)
-        conv_splitk_reduce_pool_launch(ctx->col, ks, B, Ho, Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
+        conv_splitk_reduce_pool_launch(ctx->col, ks, B, Ho, Wo, l.cout_pad, bias, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
     else
-        conv_splitk_reduce_launch(ctx->col, ks, (long)B * Ho * Wo, l.cout_pad, ctx->blob + l.b_off, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
+        conv_splitk_reduce_launch(ctx->col, ks, (long)B * Ho * Wo, l.cout_pad, bias, l.relu, out, out_cs, std::min(l.cout_pad, out_cs), ctx->stream);
 }
 
 // The Winograd kernel a layer takes, decided before anything is launched.
@@ -797,7 +828,7 @@ int run_wino(hp3d_ctx* ctx, const ConvL& l, const WinoPick& w, ConvParams p, int
             ++ctx->conv_wino_launches;
         }
     }
-    if (w.ks > 1) splitk_reduce(ctx, l, w.ks, B, Ho, Wo, pool, out, out_cs);
+    if (w.ks > 1) splitk_reduce(ctx, l, p.bias, w.ks, B, Ho, Wo, pool, out, out_cs);
     return 0;
 }
 
@@ -812,7 +843,7 @@ int run_conv_first(hp3d_ctx* ctx, const ConvL& l, const ConvParams& p, double fl
     // The pass runs on the child context's stream BESIDE the convolution (it is ahead of the gathers after the first few tiles and
     // needs 16 registers per wave next to the convolution's 3 x 160): its 13 us disappear; in this stream when there is no second one.
     KidFork beside;            // (joined when this function returns: the call's completion covers the read pass)
-    if (ctx->d_keys && (ctx->first_touch == 1 || (ctx->first_touch < 0 && !ctx->trunk_input_hot && img_bytes >= (8u << 20) && img_bytes <= (128u << 20)))) {
+    if (l.net && ctx->d_keys && (ctx->first_touch == 1 || (ctx->first_touch < 0 && !ctx->trunk_input_hot && img_bytes >= (8u << 20) && img_bytes <= (128u << 20)))) {
         if (ctx->first_touch_beside && !ctx->use_graph && !ctx->shared_weights && !ctx->two_streams_live && kid_sync_state(ctx) == 0) {
             CHK(beside.fork(ctx));          // (whatever produced the image on this stream comes first)
             touch_launch(p.in, px * 3, (float*)ctx->d_keys, ctx->kid->stream);
@@ -830,11 +861,19 @@ int run_conv_first(hp3d_ctx* ctx, const ConvL& l, const ConvParams& p, double fl
     return 0;
 }
 
+// Where a layer's filters are: the blobs its offsets refer to, and its raw HWIO filter for conv_impl=naive.
+struct ConvW {
+    const float* f32;
+    const hp3d_f16* f16;
+    const float* hwio;
+};
+
 // in: [B,H,W,in_cs] (engine channels start at `in`), out: [B,Ho',Wo',out_cs] channel 0 at `out`.
 // f16 = 1 (trunk nets after hp3d_finalize_weights(dtype=1)): `in` / `out` hold halves (except the raw image of
 // conv1_1 and out_f32 heads); in_cs / out_cs are then counted in ELEMENTS of the respective tensor.
-int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, int H, int W, float* out, int out_cs,
+int run_conv(hp3d_ctx* ctx, const ConvW& wts, const ConvL& l, const float* in, int in_cs, int B, int H, int W, float* out, int out_cs,
              int pool, int* Ho_out, int* Wo_out, int f16 = 0, int out_f32 = 0) {
+    const float* const bias = wts.f32 + l.b_off;
     int Ho, Wo, pt, pl;
     const int k = l.ek;
     same_pad(H, k, l.stride, &Ho, &pt);
@@ -845,7 +884,7 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
     if (l.hwio_off && ctx->tiny_gemm && !f16 && !pool && !ctx->conv_naive && l.stride == 2 && l.k == 3 && H == 8 && W == 8 && in_cs == l.cin && out_cs == l.cout) {
         // the last stride-2 layer of a lifting tower: 16 output pixels per image -- a split-K GEMM over them (glue.hip: conv_s2_gemm_launch)
         ProfScope ps(ctx, l.name, "conv_s2_gemm", flops, bytes);
-        conv_s2_gemm_launch(in, B, 8, l.cin, ctx->blob + l.hwio_off, ctx->blob + l.b_off, l.cout, l.relu, out, ctx->d_fcpart, ctx->stream);
+        conv_s2_gemm_launch(in, B, 8, l.cin, wts.f32 + l.hwio_off, bias, l.cout, l.relu, out, ctx->d_fcpart, ctx->stream);
         ++ctx->conv_s2_gemm_launches;
         HIPCHK(ctx, hipGetLastError());
         if (Ho_out) *Ho_out = Ho;
@@ -854,18 +893,18 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
     }
     const WinoPick wp = pick_wino(ctx, l, in_cs, out_cs, B, Ho, Wo, pool, f16);
     if (wp.kind != WINO_NONE) {
-        CHK(run_wino(ctx, l, wp, conv_params(in, ctx->blob + wp.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo, l.cin_pad, in_cs, l.cout_pad,
+        CHK(run_wino(ctx, l, wp, conv_params(in, wts.f32 + wp.w_off, bias, out, B, H, W, Ho, Wo, l.cin_pad, in_cs, l.cout_pad,
                                               out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu), pool, flops, bytes));
     } else if (l.mode == 1 && !pool && !out_f32 && ctx->use_first && !ctx->conv_naive &&
                conv_first_eligible(l.k, l.stride, l.cin, l.cout, B, H, W, out_cs, f16)) {
-        ConvParams p = conv_params(in, ctx->blob + l.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo, 3, 3, 64, out_cs, 64, pt, pl, l.relu);
+        ConvParams p = conv_params(in, wts.f32 + l.w_off, bias, out, B, H, W, Ho, Wo, 3, 3, 64, out_cs, 64, pt, pl, l.relu);
         p.im2col = 1; p.f16 = f16;
         CHK(run_conv_first(ctx, l, p, flops, bytes));
     } else if (f16 && ctx->use_h16 && !ctx->conv_naive &&
                ((l.mode == 0 && l.k == 3) || (ctx->h16_k7k1 && ((l.k == 7 && (l.mode == 0 || l.mode == 2)) || (l.k == 1 && l.mode == 0)))) &&
                conv_h16_eligible(ctx->use_h16, l.k, l.stride, l.cin_pad16 / 2, l.cout_pad, Ho, Wo, B, out_f32, out_cs) &&
                ((uintptr_t)out & 15) == 0 && !(pool && ((Ho | Wo) & 1))) {
-        ConvParams p = conv_params(in, (const float*)(ctx->blob16 + l.w16_off), ctx->blob + l.b_off, out, B, H, W, Ho, Wo, l.cin_pad16 / 2, in_cs / 2,
+        ConvParams p = conv_params(in, (const float*)(wts.f16 + l.w16_off), bias, out, B, H, W, Ho, Wo, l.cin_pad16 / 2, in_cs / 2,
                                    l.cout_pad, out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu);
         p.f16 = 1;
         ProfScope ps(ctx, l.name, l.k == 7 ? "conv_h16_7x7" : l.k == 1 ? "conv_h16_1x1" : pool ? "conv_h16_3x3_pool" : "conv_h16_3x3", flops, bytes);
@@ -873,7 +912,7 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
         if (conv_h16_launch(p, pool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_h16 launch failed for %s", l.name.c_str());
     } else if (ctx->conv_naive && l.mode == 0 && !pool && !f16) {
         ProfScope ps(ctx, l.name, "conv_naive", flops, bytes);
-        conv_naive_launch(in, B, H, W, l.cin, in_cs, ctx->naive_w[l.name], ctx->blob + l.b_off, l.k, l.stride, l.cout,
+        conv_naive_launch(in, B, H, W, l.cin, in_cs, wts.hwio, bias, l.k, l.stride, l.cout,
                           l.relu, out, out_cs, Ho, Wo, pt, pl, ctx->stream);
     } else {
         ConvPlan plan;
@@ -882,7 +921,7 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "no conv_mfma variant for %s (k=%d s=%d)", l.name.c_str(), k, l.stride);
         if (l.mode == 1 || (f16 && !out_f32)) plan.ksplit = 1;          // split-K partials are float32
         if (plan.ksplit > 1) CHK(ensure_col(ctx, (size_t)plan.ksplit * B * Ho * Wo * l.cout_pad));
-        ConvParams p = conv_params(in, f16 ? (const float*)(ctx->blob16 + l.w16_off) : ctx->blob + l.w_off, ctx->blob + l.b_off, out, B, H, W, Ho, Wo,
+        ConvParams p = conv_params(in, f16 ? (const float*)(wts.f16 + l.w16_off) : wts.f32 + l.w_off, bias, out, B, H, W, Ho, Wo,
                                    cin_units, (f16 && l.mode != 1) ? in_cs / 2 : in_cs, l.cout_pad, out_cs, std::min(l.cout_pad, out_cs), pt, pl, l.relu);
         p.f16 = f16; p.out_f32 = out_f32;
         p.tiles_x = (Wo + plan.tw - 1) / plan.tw; p.tiles_y = (Ho + plan.th - 1) / plan.th;
@@ -894,12 +933,23 @@ int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, i
         if (conv_mfma_launch(p, k, l.stride, pool, plan, ctx->stream) != 0)
             HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed for %s", l.name.c_str());
         ++ctx->conv_mfma_launches;
-        if (plan.ksplit > 1) splitk_reduce(ctx, l, plan.ksplit, B, Ho, Wo, pool, out, out_cs, false);      // (conv_mfma_plan splits no pooled layer)
+        if (plan.ksplit > 1) splitk_reduce(ctx, l, p.bias, plan.ksplit, B, Ho, Wo, pool, out, out_cs, false);      // (conv_mfma_plan splits no pooled layer)
     }
     HIPCHK(ctx, hipGetLastError());
     if (Ho_out) *Ho_out = pool ? Ho / 2 : Ho;
     if (Wo_out) *Wo_out = pool ? Wo / 2 : Wo;
     return 0;
+}
+
+// A layer of the networks: its filters are in the context's blobs
+int run_conv(hp3d_ctx* ctx, const ConvL& l, const float* in, int in_cs, int B, int H, int W, float* out, int out_cs,
+             int pool, int* Ho_out, int* Wo_out, int f16 = 0, int out_f32 = 0) {
+    const float* hwio = nullptr;
+    if (ctx->conv_naive) {
+        auto it = ctx->naive_w.find(l.name);
+        if (it != ctx->naive_w.end()) hwio = it->second;
+    }
+    return run_conv(ctx, ConvW{ctx->blob, ctx->blob16, hwio}, l, in, in_cs, B, H, W, out, out_cs, pool, Ho_out, Wo_out, f16, out_f32);
 }
 
 const ConvL& CL(hp3d_ctx* ctx, const char* name) { return ctx->T.conv[ctx->T.conv_idx.at(name)]; }
@@ -1963,29 +2013,7 @@ int hp3d_finalize_weights(hp3d_ctx* ctx, int dtype) {
         if (!ok) continue;
         const ConvL* lp = &l;
         float* hp = host.data();
-        pack_tasks.push_back([lp, w, b, hp]() {
-            const ConvL& l = *lp;
-            pack_conv(l, w->data.data(), b->data.data(), hp);
-            if (l.raw_off)          // lift_fused.hip: [cout block of 64][cin4][tap][64], zero rows / columns as padding
-                for (int t = 0; t < 9; ++t)
-                    for (int c = 0; c < l.cin; ++c)
-                        for (int co = 0; co < l.cout; ++co)
-                            hp[l.raw_off + (((size_t)(co >> 6) * l.cin4 + c) * 9 + t) * 64 + (co & 63)] = w->data[((size_t)t * l.cin + c) * l.cout + co];
-            if (l.hwio_off) memcpy(hp + l.hwio_off, w->data.data(), sizeof(float) * (size_t)9 * l.cin * l.cout);
-            if (l.ww_off) {      // U = G g G^T in the Winograd kernels' fragment orders
-                std::vector<int> cmap(l.cin_pad, -1);
-                for (int e = 0; e < l.cin_pad; ++e) {
-                    if (l.mode == 0) cmap[e] = e < l.cin ? e : -1;
-                    else if (e < 128) cmap[e] = 21 + e;            // concat buffer [encoding | scoremap | 0] vs reference [scoremap, encoding]
-                    else if (e < 149) cmap[e] = e - 128;
-                }
-                wino_pack_weights(w->data.data(), l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), hp + l.ww_off);
-                wino2_pack_weights(w->data.data(), l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), hp + l.ww2_off);
-                if (l.ww4_off) wino4_pack_weights(w->data.data(), l.k, l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), hp + l.ww4_off);
-                if (l.ww7_off) wino7_pack_weights(w->data.data(), l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), hp + l.ww7_off);
-                if (l.ww4s_off) wino4s_pack_weights(w->data.data(), l.cin, l.cout, l.cin_pad, l.cout_pad, cmap.data(), hp + l.ww4s_off);
-            }
-        });
+        pack_tasks.push_back([lp, w, b, hp]() { pack_layer(*lp, w->data.data(), b->data.data(), hp); });
     }
     {
         std::atomic<size_t> next{0};
@@ -2295,174 +2323,50 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
     if (!ctx) return HP3D_ERR_ARG;
     if (!x || !w_hwio || !bias || !out || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1)
         HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (ctx->conv_naive && pool) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "naive conv has no fused pool");
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->profiling != 2) prof_reset(ctx);
     ConvL l;
     l.name = "op/conv2d";
     l.k = k; l.cin = Cin; l.cout = Cout; l.stride = stride; l.relu = act; l.net = 0;
-    l.mode = 0; l.ek = k; l.cin_pad = pad32(Cin); l.cout_pad = pad32(Cout);
-    if (ctx->use_wino == 2 && !ctx->conv_naive && (k == 3 || k == 7) && stride == 1) {       // conv_impl=winograd: no silent fallback
-        l.cin_pad = (Cin + 63) / 64 * 64;
-        if (Cout % 64) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_impl=winograd needs Cout %% 64 == 0 (got %d)", Cout);
+    // the conv1_1 shape (nets/ColorHandPose3DNetwork.py:144,183) runs as the networks' first layer (32 x 64 im2col filters, conv_first.hip);
+    // every other Cin = 3 layer as a plain one: the im2col form sums in another order
+    l.mode = k == 3 && Cin == 3 && Cout == 64 && !pool && ctx->use_first && ctx->use_wino != 2 && conv_first_eligible(k, stride, Cin, Cout, B, H, W, Cout, 0);
+    l.ek = l.mode ? 1 : k; l.cin_pad = pad32(Cin); l.cout_pad = pad32(Cout);
+    // The Winograd sections are the op's selection rule (pick_wino takes a form whose section exists): a form whose option is forced
+    // to "1", else F(2x2,3x3) where conv_wino_eligible allows -- no cost model -- and all of them for Cout % 64 == 0 only.
+    int secs = 0;
+    if (ctx->use_wino && !l.mode && (k == 3 || k == 7) && stride == 1) {
+        if (ctx->use_wino == 2) {       // conv_impl=winograd: no silent fallback
+            l.cin_pad = (Cin + 63) / 64 * 64;
+            if (Cout % 64) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_impl=winograd needs Cout %% 64 == 0 (got %d)", Cout);
+        }
+        if (Cout % 64 == 0)
+            secs = SEC_WINO | (ctx->use_wino2 == 1 ? SEC_WINO2 : 0) | (ctx->use_wino4 == 1 ? SEC_WINO4 : 0) |
+                   (ctx->use_wino4s == 1 && k == 3 ? SEC_WINO4S : 0) | (ctx->use_wino7 == 1 && k == 7 ? SEC_WINO7 : 0);
     }
-    l.w_off = 0; l.b_off = (size_t)k * k * l.cin_pad * l.cout_pad;
-    std::vector<float> packed(l.b_off + l.cout_pad);
-    pack_conv(l, w_hwio, bias, packed.data());
-    int Ho, Wo, pt, pl;
-    same_pad(H, k, stride, &Ho, &pt);
-    same_pad(W, k, stride, &Wo, &pl);
-    const int Hs = pool ? Ho / 2 : Ho, Ws = pool ? Wo / 2 : Wo;
+    size_t floats = 0, halves = 0;
+    reserve_conv(l, secs, floats, halves);
+    std::vector<float> packed(floats, 0.f);
+    pack_layer(l, w_hwio, bias, packed.data());
+    const int in_cs = l.mode ? Cin : l.cin_pad;
     Scratch S(ctx);
+    float* d_pk = S.upload(packed.data(), packed.size()); NN(ctx, d_pk);
+    float* d_w = nullptr;
+    if (ctx->conv_naive) { d_w = S.upload(w_hwio, (size_t)k * k * Cin * Cout); NN(ctx, d_w); }
     float* d_x = S.upload(x, (size_t)B * H * W * Cin); NN(ctx, d_x);
-    float* d_xp = d_x;
-    if (l.cin_pad != Cin) {
-        d_xp = S.alloc<float>((size_t)B * H * W * l.cin_pad); NN(ctx, d_xp);
-        pad_channels_launch(d_x, B * H * W, Cin, d_xp, l.cin_pad, ctx->stream);
+    if (in_cs != Cin) {
+        float* d_xp = S.alloc<float>((size_t)B * H * W * in_cs); NN(ctx, d_xp);
+        pad_channels_launch(d_x, B * H * W, Cin, d_xp, in_cs, ctx->stream);
+        d_x = d_xp;
     }
-    float* d_out = S.alloc<float>((size_t)B * Hs * Ws * Cout); NN(ctx, d_out);
-    if (k == 3 && Cin == 3 && Cout == 64 && !pool && ctx->use_first && !ctx->conv_naive && ctx->use_wino != 2 &&
-        conv_first_eligible(k, stride, Cin, Cout, B, H, W, Cout, 0)) {
-        // the conv1_1 shape (nets/ColorHandPose3DNetwork.py:144,183) runs on the networks' own first-layer kernel (conv_first.hip)
-        ConvL l1 = l;
-        l1.mode = 1; l1.ek = 1; l1.cin_pad = 32; l1.cout_pad = 64;
-        l1.w_off = 0; l1.b_off = (size_t)32 * 64;
-        std::vector<float> pk1(l1.b_off + 64);
-        pack_conv(l1, w_hwio, bias, pk1.data());
-        float* d_pk = S.upload(pk1.data(), pk1.size()); NN(ctx, d_pk);
-        ConvParams p = conv_params(d_x, d_pk, d_pk + l1.b_off, d_out, B, H, W, Ho, Wo, 3, 3, 64, 64, 64, pt, pl, act);
-        p.im2col = 1;
-        conv_first_launch(p, ctx->stream, ctx->first_balanced);
-        ++ctx->conv_first_launches;
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)B * Hs * Ws * Cout, hipMemcpyDeviceToHost, ctx->stream));
-        return finish_op(ctx);
-    }
-    int op_ks7 = 1;
-    if (ctx->use_wino && ctx->use_wino7 == 1 && !ctx->conv_naive && k == 7 && !pool && Cout % 64 == 0 &&
-        conv_wino7_eligible(k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, nullptr, ctx->wino_splitk ? &op_ks7 : nullptr)) {
-        op_ks7 = wino7_ks_override(ctx, op_ks7, l.cin_pad, (long)B * Ho * Wo * Cout);
-        // option "wino7" = "1": the F(4x4,4x4) form of a 7x7 filter (conv_wino7.hip)
-        const size_t wn = wino7_packed_floats(l.cin_pad, l.cout_pad);
-        std::vector<float> pw(wn + l.cout_pad, 0.f);
-        wino7_pack_weights(w_hwio, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
-        for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
-        float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
-        p.ksplit = op_ks7; p.nsub = 4;
-        float* d_part7 = nullptr;
-        if (op_ks7 > 1) {          // under-filled launch: raw partial sums per channel split, then the deterministic reduce
-            d_part7 = S.alloc<float>((size_t)op_ks7 * B * Ho * Wo * Cout); NN(ctx, d_part7);
-            p.out = d_part7;
-        }
-        if (conv_wino7_launch(p, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,4x4)): launch refused");
-        if (op_ks7 > 1) {
-            conv_splitk_reduce_launch(d_part7, op_ks7, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
-            ++ctx->conv_splitk_reduce_launches;
-        }
-        ++ctx->conv_wino7_launches;
-        ctx->conv_wino7_split_launches += op_ks7 > 1;
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)B * Hs * Ws * Cout, hipMemcpyDeviceToHost, ctx->stream));
-        return finish_op(ctx);
-    }
-    if (ctx->use_wino && ctx->use_wino4s == 1 && !ctx->conv_naive && Cout % 64 == 0 &&
-        conv_wino4s_eligible(k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, pool, nullptr)) {
-        // option "wino4_split" = "1": the F(4x4,3x3) kernel with split bfloat16 operands (conv_wino4s.hip)
-        const size_t wn = (wino4s_packed_bytes(l.cin_pad, l.cout_pad) + 15) / 16 * 4;
-        std::vector<float> pw(wn + l.cout_pad, 0.f);
-        wino4s_pack_weights(w_hwio, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
-        for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
-        float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
-        if (ctx->w4_tail && conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
-            p.partial = S.alloc<float>(conv_wino4s_tail_floats()); NN(ctx, p.partial);
-            p.partial_cap = conv_wino4s_tail_floats();
-        }
-        const int lr = conv_wino4s_launch(p, pool, ctx->stream);
-        if (lr < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (F(4x4,3x3), split operands): launch refused");
-        if (lr == 1) ++ctx->conv_wino4s_tail_launches;
-        ++ctx->conv_wino4s_launches;
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)B * Hs * Ws * Cout, hipMemcpyDeviceToHost, ctx->stream));
-        return finish_op(ctx);
-    }
-    int op_ks = 1, op_ks2 = 1;
-    const bool op4 = ctx->use_wino && ctx->use_wino4 == 1 && !ctx->conv_naive && Cout % 64 == 0 &&
-        conv_wino4_eligible(k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, pool, ctx->wino_splitk ? &op_ks2 : nullptr);
-    if (op4 || (ctx->use_wino && ctx->use_wino2 == 1 && !ctx->conv_naive && Cout % 64 == 0 &&
-        conv_wino2_eligible(k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, pool, ctx->wino_splitk ? &op_ks2 : nullptr))) {
-        // option "wino4" = "1": the F(4x4,3x3) kernel (conv_wino4.hip); option "wino2" = "1": the two-workgroups-per-CU F(2x2,3x3) kernel
-        const size_t wn = op4 ? wino4_packed_floats(k, l.cin_pad, l.cout_pad) : wino_packed_floats(k, l.cin_pad, l.cout_pad);
-        std::vector<float> pw(wn + l.cout_pad, 0.f);
-        if (op4) wino4_pack_weights(w_hwio, k, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
-        else wino2_pack_weights(w_hwio, k, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
-        for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
-        float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
-        p.ksplit = op_ks2; p.nsub = k == 7 ? 9 : 1;
-        float* d_part = nullptr;
-        if (op_ks2 > 1) {
-            d_part = S.alloc<float>((size_t)op_ks2 * B * Ho * Wo * Cout); NN(ctx, d_part);
-            p.out = d_part;
-        } else if (op4 && k == 3 && ctx->w4_tail &&
-                   conv_wino4_tail_plan(l.cin_pad, l.cout_pad, Ho, Wo, B, nullptr) > 0) {
-            p.partial = S.alloc<float>(conv_wino4_tail_floats()); NN(ctx, p.partial);         // tail pieces (conv_wino4.hip, TAIL)
-            p.partial_cap = conv_wino4_tail_floats();
-        }
-        const int lr = op4 ? conv_wino4_launch(p, op_ks2 > 1 ? 0 : pool, ctx->stream) : conv_wino2_launch(p, op_ks2 > 1 ? 0 : pool, ctx->stream);
-        if (lr < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv (%s): launch refused", op4 ? "F(4x4,3x3)" : "2 workgroups per CU");
-        if (op4 && lr == 1) ++ctx->conv_wino4_tail_launches;
-        ++(op4 ? ctx->conv_wino4_launches : ctx->conv_wino2_launches);
-        if (op_ks2 > 1 && pool)
-            conv_splitk_reduce_pool_launch(d_part, op_ks2, B, Ho, Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
-        else if (op_ks2 > 1)
-            conv_splitk_reduce_launch(d_part, op_ks2, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
-        ctx->conv_splitk_reduce_launches += op_ks2 > 1;
-    } else if (ctx->use_wino && !ctx->conv_naive && conv_wino_eligible(ctx->use_wino, k, stride, l.cin_pad, l.cout_pad, Ho, Wo, B, l.cin_pad, Cout, pool, ctx->wino_splitk ? &op_ks : nullptr) && Cout % 64 == 0) {
-        const size_t wn = wino_packed_floats(k, l.cin_pad, l.cout_pad);
-        std::vector<float> pw(wn + l.cout_pad, 0.f);
-        wino_pack_weights(w_hwio, k, Cin, Cout, l.cin_pad, l.cout_pad, nullptr, pw.data());
-        for (int co = 0; co < Cout; ++co) pw[wn + co] = bias[co];
-        float* d_pk = S.upload(pw.data(), pw.size()); NN(ctx, d_pk);
-        ConvParams p = conv_params(d_xp, d_pk, d_pk + wn, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
-        p.tiles_x = (Wo + 15) / 16; p.tiles_y = (Ho + 7) / 8;
-        p.ksplit = op_ks; p.nsub = k == 7 ? 9 : 1;
-        float* d_part = nullptr;
-        if (op_ks > 1) {
-            d_part = S.alloc<float>((size_t)op_ks * B * Ho * Wo * Cout); NN(ctx, d_part);
-            p.out = d_part;
-        }
-        if (conv_wino_launch(p, op_ks > 1 ? 0 : pool, ctx->stream)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "winograd conv: tensor exceeds 32-bit offsets");
-        ++ctx->conv_wino_launches;
-        if (op_ks > 1 && pool)
-            conv_splitk_reduce_pool_launch(d_part, op_ks, B, Ho, Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
-        else if (op_ks > 1)
-            conv_splitk_reduce_launch(d_part, op_ks, (long)B * Ho * Wo, Cout, d_pk + wn, act, d_out, Cout, Cout, ctx->stream);
-        ctx->conv_splitk_reduce_launches += op_ks > 1;
-    } else if (ctx->conv_naive) {
-        if (pool) HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "naive conv has no fused pool");
-        float* d_w = S.upload(w_hwio, (size_t)k * k * Cin * Cout); NN(ctx, d_w);
-        float* d_b = S.upload(bias, (size_t)Cout); NN(ctx, d_b);
-        conv_naive_launch(d_x, B, H, W, Cin, Cin, d_w, d_b, k, stride, Cout, act, d_out, Cout, Ho, Wo, pt, pl, ctx->stream);
-    } else {
-        float* d_pk = S.upload(packed.data(), packed.size()); NN(ctx, d_pk);
-        ConvPlan plan;
-        if (conv_mfma_plan(k, stride, Ho, Wo, l.cin_pad, l.cout_pad, pool, B, &plan) != 0)
-            HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "no conv_mfma variant for k=%d stride=%d pool=%d", k, stride, pool);
-        float* d_part = nullptr;
-        if (plan.ksplit > 1) { d_part = S.alloc<float>((size_t)plan.ksplit * B * Ho * Wo * l.cout_pad); NN(ctx, d_part); }
-        ConvParams p = conv_params(d_xp, d_pk, d_pk + l.b_off, d_out, B, H, W, Ho, Wo, l.cin_pad, l.cin_pad, l.cout_pad, Cout, Cout, pt, pl, act);
-        p.tiles_x = (Wo + plan.tw - 1) / plan.tw; p.tiles_y = (Ho + plan.th - 1) / plan.th;
-        p.ksplit = plan.ksplit; p.partial = d_part;
-        if (conv_mfma_launch(p, k, stride, pool, plan, ctx->stream) != 0)
-            HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "conv_mfma launch failed");
-        ++ctx->conv_mfma_launches;
-        if (plan.ksplit > 1)
-            conv_splitk_reduce_launch(d_part, plan.ksplit, (long)B * Ho * Wo, l.cout_pad, p.bias, act, d_out, Cout, Cout,
-                                      ctx->stream);
-        ctx->conv_splitk_reduce_launches += plan.ksplit > 1;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)B * Hs * Ws * Cout, hipMemcpyDeviceToHost, ctx->stream));
+    int Ho, Wo, pad;
+    same_pad(H, k, stride, &Ho, &pad);
+    same_pad(W, k, stride, &Wo, &pad);
+    const size_t out_floats = (size_t)B * (pool ? Ho / 2 : Ho) * (pool ? Wo / 2 : Wo) * Cout;
+    float* d_out = S.alloc<float>(out_floats); NN(ctx, d_out);
+    CHK(run_conv(ctx, ConvW{d_pk, nullptr, d_w}, l, d_x, in_cs, B, H, W, d_out, Cout, pool, nullptr, nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
 

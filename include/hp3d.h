@@ -268,6 +268,13 @@ int hp3d_pose3d(hp3d_ctx* ctx, int B, const float* scoremap32, const float* hand
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65
  *                      x [B,H,W,Cin], w HWIO, SAME padding incl. the asymmetric stride-2 case.
+ *                      The call describes one layer ("op/conv2d"), packs its filters and runs it through the executor's
+ *                      own convolution dispatch: same kernel choice code, same launch parameters as a network layer, except
+ *                      that no cost model is asked (a Winograd form runs where its option is forced to "1", F(2x2,3x3)
+ *                      where the shape allows, all for Cout % 64 == 0 only) and no first-touch pass is issued.  Partial
+ *                      sums of channel splits and tail pieces live in the context's scratch (grown on demand, kept until
+ *                      hp3d_destroy), and with profiling on the call records its launches as rows named "op/conv2d"
+ *                      (stage 1 of hp3d_get_timing).
  * hp3d_maxpool2        NetworkOps.max_pool, 2x2/2 VALID                       utils/general.py:61-65
  * hp3d_avgpool8        tf.nn.avg_pool 8x8/8                                   nets/PosePriorNetwork.py:61
  * hp3d_resize_bilinear tf.image.resize_images (TF1.3 legacy bilinear)         nets/ColorHandPose3DNetwork.py:97,128,166
