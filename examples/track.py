@@ -1,0 +1,64 @@
+#!/usr/bin/env python
+"""Tracking a hand through the frames of a video on the MI355X engine: the first frame detects the hand with
+HandSegNet, every later frame crops with the box derived from the previous frame's keypoints and runs no HandSegNet at all --
+until a frame reports the hand as lost, which makes the next one detect again.
+
+    python examples/track.py frames_dir/                  (*.png / *.jpg in name order; needs ./weights/*.pickle, like run.py)
+    python examples/track.py frames.npy                   (uint8 or float [N,H,W,3])
+    python examples/track.py --synthetic                  (seeded synthetic weights + frames)
+"""
+import glob
+import json
+import os
+import tempfile
+
+import numpy as np
+
+from common import parser, synthetic_weight_files
+
+if __name__ == '__main__':
+    ap = parser(__doc__)
+    ap.add_argument('frames', nargs='?')
+    ap.add_argument('--redetect', type=int, default=0, help='every N-th frame detects anew (0: only when the hand is lost)')
+    ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
+    ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
+                    help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
+    a = ap.parse_args()
+    if not a.synthetic and not a.frames:
+        ap.error('give a directory of frames or a .npy file (or --synthetic)')
+    from hand3d_amd import synth
+    from hand3d_amd.nets.ColorHandPose3DNetwork import ColorHandPose3DNetwork
+
+    net = ColorHandPose3DNetwork(device=a.device)
+    if a.synthetic:
+        net.init(None, weight_files=synthetic_weight_files(tempfile.mkdtemp()))
+        base = (synth.make_image(0) + 0.5) * 255.0
+        frames = [np.roll(base, 3 * i, axis=1) for i in range(8)]          # the same scene drifting to the right
+    else:
+        net.init(None, weight_files=['%s/handsegnet-rhd.pickle' % a.weights_dir,
+                                     '%s/posenet3d-rhd-stb-slr-finetuned.pickle' % a.weights_dir])
+        if a.frames.endswith('.npy'):
+            frames = list(np.load(a.frames))
+        else:
+            try:
+                from PIL import Image
+            except ImportError:
+                ap.error('reading image files needs Pillow; pass the frames as a .npy array instead')
+            paths = sorted(p for ext in ('png', 'jpg', 'jpeg') for p in glob.glob(os.path.join(a.frames, '*.' + ext)))
+            frames = [np.asarray(Image.open(p).convert('RGB')) for p in paths]
+    net.engine.set_option('track_redetect', str(a.redetect))
+    net.engine.set_option('track_min_score', a.min_score)
+    hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
+    net.track_reset()
+    for i, frame in enumerate(frames):
+        frame = np.asarray(frame)
+        if frame.dtype == np.uint8:
+            image_v = frame[None]                      # tracked steps crop straight from the uint8 frame
+        elif a.float_range == '255':
+            image_v = frame[None].astype(np.float32) / 255.0 - 0.5
+        else:
+            image_v = frame[None].astype(np.float32)
+        coord3d, kp_hw, kp_hw_crop, scale, center, confidence, lost, detected = net.track(image_v, hand_side_v)
+        print(json.dumps({'frame': i, 'step': 'detect' if detected[0] else 'tracked', 'center': center[0].tolist(),
+                          'scale': float(scale[0, 0]), 'confidence': float(confidence[0]), 'lost': int(lost[0]),
+                          'wrist_hw': kp_hw[0, 0].tolist(), 'wrist_xyz': coord3d[0, 0].tolist()}))

@@ -59,6 +59,13 @@ _SIGNATURES = {
     'hp3d_resize_bilinear': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_crop_and_resize': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p]),
+    'hp3d_track_reset': (C.c_int, [_ctx]),
+    'hp3d_track_seed': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'hp3d_track_step': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    'hp3d_track_step_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
+    'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'hp3d_mask_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'hp3d_fc': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_argmax2d': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -311,6 +318,86 @@ class Engine(object):
         else:
             self._chk(self.lib.hp3d_infer_full_dev(self.h, B, H, W, v(image_ptr), v(hand_side_ptr), v(scoremap), v(crop),
                                                    v(scale), v(center), v(kpmap), v(coord3d), v(mask)))
+
+    # -- tracking: a hand across video frames (include/hp3d.h) -------------------------
+    def track_reset(self):
+        """The next track_step detects (HandSegNet) whatever the previous step found."""
+        self._chk(self.lib.hp3d_track_reset(self.h))
+
+    def track_seed(self, center, scale, H, W):
+        """Start from boxes the caller has: center [B,2] (row, col), scale [B]; the next step at (B, H, W) is a tracked one."""
+        center, scale = _f32(center), _f32(scale).reshape(-1)
+        B = scale.shape[0]
+        assert center.shape == (B, 2), "center must be [B,2]"
+        self._chk(self.lib.hp3d_track_seed(self.h, B, int(H), int(W), _ptr(center), _ptr(scale)))
+
+    @staticmethod
+    def _track_outputs(B, want_kpmap):
+        return {'crop': np.empty((B, 256, 256, 3), np.float32), 'scale': np.empty((B, 1), np.float32),
+                'center': np.empty((B, 2), np.float32),
+                'kpmap': np.empty((B, 256, 256, 21), np.float32) if want_kpmap else None,
+                'coord3d': np.empty((B, 21, 3), np.float32), 'kp_crop': np.empty((B, 21, 2), np.int32),
+                'kp_hw': np.empty((B, 21, 2), np.float64), 'confidence': np.empty((B,), np.float32),
+                'lost': np.empty((B,), np.int32), 'detected': np.empty((B,), np.int32)}
+
+    _TRACK_ORDER = ('crop', 'scale', 'center', 'kpmap', 'coord3d', 'kp_crop', 'kp_hw', 'confidence', 'lost', 'detected')
+
+    def track_step(self, image, hand_side, want_kpmap=False):
+        """One video step on float32 frames [B,H,W,3]: a detect step (HandSegNet) or a tracked step (crop from the previous step's
+        keypoints).  Returns a dict: crop, scale, center (the boxes this step used), kpmap (or None), coord3d, kp_crop, kp_hw,
+        confidence, lost (about the NEXT box), detected (1 where this step's box came from HandSegNet)."""
+        image, hand_side = _f32(image), _f32(hand_side)
+        assert image.ndim == 4 and image.shape[3] == 3, "image must be [B,H,W,3]"
+        B, H, W, _ = image.shape
+        assert hand_side.shape == (B, 2), "hand_side must be [B,2]"
+        o = self._track_outputs(B, want_kpmap)
+        self._chk(self.lib.hp3d_track_step(self.h, B, H, W, _ptr(image), _ptr(hand_side), *[_ptr(o[k]) for k in self._TRACK_ORDER]))
+        return o
+
+    def track_step_u8(self, image_u8, hand_side, H=None, W=None, want_kpmap=False):
+        """track_step on uint8 frames [B,Hin,Win,3]; tracked steps crop straight from them.  (H, W) default to the frame size,
+        the only size the engine accepts here."""
+        img = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        hand_side = _f32(hand_side)
+        assert img.ndim == 4 and img.shape[3] == 3, "image must be [B,Hin,Win,3] uint8"
+        B, Hin, Win, _ = img.shape
+        assert hand_side.shape == (B, 2), "hand_side must be [B,2]"
+        o = self._track_outputs(B, want_kpmap)
+        self._chk(self.lib.hp3d_track_step_u8(self.h, B, Hin, Win, _ptr(img), int(H or Hin), int(W or Win), _ptr(hand_side),
+                                              *[_ptr(o[k]) for k in self._TRACK_ORDER]))
+        return o
+
+    def track_step_dev(self, B, H, W, image_ptr, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0, coord3d=0, kp_crop=0, kp_hw=0,
+                       confidence=0, lost=0, detected=0):
+        """Device-pointer variant (ints); stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_step_dev(self.h, B, H, W, v(image_ptr), v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap),
+                                               v(coord3d), v(kp_crop), v(kp_hw), v(confidence), v(lost), v(detected)))
+
+    def track_box(self, keypoint_hw, H, W, score32=None, margin=None):
+        """The next crop box from 21 image-space keypoints [B,21,2] (row, col): (center [B,2], scale [B], confidence [B], lost [B]).
+        margin=None uses option "track_margin"; margin=1 is the dataset readers' hand_crop rule bit for bit."""
+        kp = np.ascontiguousarray(keypoint_hw, dtype=np.float64)
+        assert kp.ndim == 3 and kp.shape[1:] == (21, 2), "keypoint_hw must be [B,21,2]"
+        B = kp.shape[0]
+        sm = None if score32 is None else _f32(score32)
+        assert sm is None or sm.shape == (B, 32, 32, 21), "score32 must be [B,32,32,21]"
+        center, scale = np.empty((B, 2), np.float32), np.empty((B,), np.float32)
+        conf, lost = np.empty((B,), np.float32), np.empty((B,), np.int32)
+        assert margin is None or margin > 0, "margin must be positive"
+        self._chk(self.lib.hp3d_track_box(self.h, B, int(H), int(W), _ptr(kp), _ptr(sm), 0.0 if margin is None else float(margin),
+                                          _ptr(center), _ptr(scale), _ptr(conf), _ptr(lost)))
+        return center, scale, conf, lost
+
+    def crop_and_resize_u8(self, image_u8, center, scale, crop_size=256):
+        """crop_and_resize straight from uint8 frames [B,H,W,3] (= preprocess_u8 at equal sizes -> crop_and_resize, bit for bit)."""
+        img = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        center, scale = _f32(center), _f32(scale).reshape(-1)
+        assert img.ndim == 4 and img.shape[3] == 3, "image must be [B,H,W,3] uint8"
+        B, H, W, _ = img.shape
+        out = np.empty((B, crop_size, crop_size, 3), np.float32)
+        self._chk(self.lib.hp3d_crop_and_resize_u8(self.h, _ptr(img), B, H, W, _ptr(center), _ptr(scale), crop_size, _ptr(out)))
+        return out
 
     def infer_2d(self, image):
         image = _f32(image)

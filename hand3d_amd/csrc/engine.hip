@@ -275,6 +275,10 @@ struct Options {
                                // (the LDS kernel only: larger frames are refused), 2 "global" (the global-scratch kernel at every size)
     int micro_batch = -1;      // whole-path calls run in chunks of at most this many images (0: never split; -1 auto:
                                // 32 in float32 mode, no split with half-precision trunks -- measured optima)
+    float track_margin = 1.25f;     // option "track_margin": factor on the tracked box's size (the detection path's own 1.25, ColorHandPose3DNetwork.py:84)
+    float track_min_score = 0.f;    // option "track_min_score": a tracked image is lost when its confidence is below this ...
+    int track_use_min_score = 0;    // ... "off" (default): never
+    int track_redetect = 0;         // option "track_redetect": every N-th tracking step is a detect step that re-boxes every image (0: never)
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -299,6 +303,26 @@ struct Counters {
     long conv_mfma_launches = 0;                    // layers that went to the general direct kernel (conv_mfma.hip, f32 and f16)
     long conv_splitk_reduce_launches = 0;           // channel-split reduces (conv_splitk_reduce*_launch)
     long mask_grow_global_launches = 0;             // mask growths on the global-scratch kernel
+    long track_detect_steps = 0, track_tracked_steps = 0;      // hp3d_track_step*: steps that ran HandSegNet / that did not
+    long crop_u8_launches = 0;                      // crops taken straight from a uint8 frame (crop_and_resize_u8_kernel)
+};
+
+// What a context knows about the hands it follows (hp3d_track_*): the boxes for the next step, on the device, and the host's copy of the
+// `lost` flags that decides whether the next step detects.  Two box buffers: a step crops from box[cur] and writes the next boxes to
+// box[cur ^ 1], so the boxes a step used are still there when its outputs are copied out.
+struct TrackState {
+    int cap = 0;                        // images the buffers hold
+    float* center[2] = {nullptr, nullptr};
+    float* scale[2] = {nullptr, nullptr};
+    float* conf = nullptr;
+    int *lost = nullptr, *detected = nullptr;
+    int* h_lost = nullptr;              // page-locked: the last step's flags (copied behind the step, ev_lost)
+    hipEvent_t ev_lost = nullptr;
+    bool pending = false;               // that copy has been enqueued and not waited for yet
+    int cur = 0;
+    bool valid = false;                 // box[cur] holds boxes for (B, H, W)
+    int B = 0, H = 0, W = 0;
+    int since = 0;                      // tracked steps since the last detect step
 };
 
 }  // namespace
@@ -360,6 +384,7 @@ struct hp3d_ctx : Options, Counters {
     long graph_epoch = 0;      // bumped by anything a captured sequence depends on (allocations, weights, options)
     unsigned* d_mgscratch = nullptr;                // the global-scratch kernel's bitmaps, B x mask_grow_global_words(H, W) words
     size_t mg_words = 0;
+    TrackState track;
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -1347,7 +1372,7 @@ int copy_out(hp3d_ctx* ctx, float* dst, const float* src, size_t n, bool dev) {
 }
 
 // stages 2-8 of the full path on device-resident image/hand_side
-int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W, int want_mask, bool image_hot = false) {
+int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W, int want_mask, bool image_hot = false, bool do_crop = true) {
     CHK(run_handsegnet(ctx, d_image, B, H, W, image_hot));
     MaskBuffers mb{ctx->d_keys, ctx->d_det, nullptr};
     {
@@ -1365,7 +1390,7 @@ int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W
                              ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->stream);
         }
     }
-    {
+    if (do_crop) {          // (a tracking step chooses its boxes first: track_step_impl)
         ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * B * (H * W * 3 + 256 * 256 * 3));
         crop_and_resize_launch(d_image, B, H, W, 3, ctx->d_center, ctx->d_scale, 256, ctx->d_crop, ctx->stream);
     }
@@ -1375,9 +1400,9 @@ int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W
 
 // detect_keypoints + trafo_coords (utils/general.py:331-357; run.py:72-73, eval2d.py:93-94) on the 32 x 32 maps of the
 // last PoseNet2D run: no 256 x 256 x 21 heat-map has to exist, let alone travel to the host
-int run_kp_detect(hp3d_ctx* ctx, int B, int32_t* kp_crop, double* kp_image, bool dev) {
+int run_kp_detect(hp3d_ctx* ctx, int B, int32_t* kp_crop, double* kp_image, bool dev, const float* scale = nullptr, const float* center = nullptr) {
     ProfScope ps(ctx, "kp_detect", "kp_detect", 0.0, 4.0 * B * 32 * 32 * 21);
-    kp_detect_launch(ctx->d_sm[2], B, 32, 32, 21, 32, 256, 256, ctx->d_scale, ctx->d_center,
+    kp_detect_launch(ctx->d_sm[2], B, 32, 32, 21, 32, 256, 256, scale ? scale : ctx->d_scale, center ? center : ctx->d_center,
                      dev && kp_crop ? kp_crop : ctx->d_kpcrop, dev && kp_image ? kp_image : ctx->d_kpimg, ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     if (!dev) {
@@ -1631,6 +1656,166 @@ int finish_op(hp3d_ctx* ctx) {
     return check_lift_error(ctx);
 }
 
+// ---- tracking ---------------------------------------------------------------------------------------
+// Device state for B images; grown on the first step / seed of a larger batch, never inside a steady-state step.
+int ensure_track(hp3d_ctx* ctx, int B) {
+    TrackState& T = ctx->track;
+    if (B <= T.cap) return 0;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }
+    for (int i = 0; i < 2; ++i) {
+        CHK(dev_realloc(ctx, &T.center[i], (size_t)B * 2));
+        CHK(dev_realloc(ctx, &T.scale[i], (size_t)B));
+    }
+    CHK(dev_realloc(ctx, &T.conf, (size_t)B));
+    CHK(dev_realloc(ctx, &T.lost, (size_t)B));
+    CHK(dev_realloc(ctx, &T.detected, (size_t)B));
+#ifdef HP3D_EMU
+    free(T.h_lost);
+    T.h_lost = (int*)malloc(sizeof(int) * (size_t)B);
+    if (!T.ev_lost) HIPCHK(ctx, hipEventCreate(&T.ev_lost));
+#else
+    if (T.h_lost) HIPCHK(ctx, hipHostFree(T.h_lost));
+    T.h_lost = nullptr;
+    HIPCHK(ctx, hipHostMalloc((void**)&T.h_lost, sizeof(int) * (size_t)B, hipHostMallocDefault));
+    if (!T.ev_lost) HIPCHK(ctx, hipEventCreateWithFlags(&T.ev_lost, hipEventDisableTiming));
+#endif
+    if (!T.h_lost) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "tracking state: host allocation failed");
+    T.cap = B;
+    T.valid = false;
+    return 0;
+}
+
+void track_free(hp3d_ctx* ctx) {
+    TrackState& T = ctx->track;
+    for (int i = 0; i < 2; ++i) {
+        if (T.center[i]) hipFree(T.center[i]);
+        if (T.scale[i]) hipFree(T.scale[i]);
+    }
+    if (T.conf) hipFree(T.conf);
+    if (T.lost) hipFree(T.lost);
+    if (T.detected) hipFree(T.detected);
+#ifdef HP3D_EMU
+    free(T.h_lost);
+#else
+    if (T.h_lost) hipHostFree(T.h_lost);
+#endif
+    if (T.ev_lost) hipEventDestroy(T.ev_lost);
+    T = TrackState();
+}
+
+// One step of a video: a DETECT step (HandSegNet -> mask -> box for the whole batch, then per image the tracked box where it is
+// still good) or a TRACKED step (no HandSegNet, no soft-max, no mask growth: the crop comes from the boxes the previous step
+// derived from its keypoints).  Behind the crop both are infer_full_impl: PoseNet2D, the lifting stage, keypoint detection -- plus
+// the one launch that turns the keypoints into the next boxes.  The step type is decided on the host, before anything is enqueued,
+// from the previous step's `lost` flags (4 * B bytes that travel behind that step); the whole batch detects when any image is lost:
+// one kernel plan per step, no gather of the lost images.  image_u8 (host, frame = network size) instead of image: the tracked
+// step crops straight from the uint8 frame, the detect step normalises it first (preprocess_u8) as hp3d_infer_full_u8 does.
+int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, const unsigned char* image_u8, const float* hand_side,
+                    float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
+                    double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev) {
+    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    CHK(check_img(ctx, B, H, W));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TrackState& T = ctx->track;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
+    const bool fresh = !T.valid || T.B != B || T.H != H || T.W != W;
+    bool any_lost = false;
+    if (!fresh)
+        for (int b = 0; b < B; ++b) any_lost = any_lost || T.h_lost[b] != 0;
+    const bool sched = ctx->track_redetect > 0 && T.since + 1 >= ctx->track_redetect;
+    const bool detect = fresh || any_lost || sched;
+    const int force_all = (fresh || sched) ? 1 : 0;      // nothing to keep / a scheduled re-detection re-boxes every image
+    CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
+    const int mb0 = auto_micro_batch(ctx, B, H, W);
+    const int mb = mb0 <= 0 ? B : std::min(mb0, B);
+    CHK(ensure_arena(ctx, mb, H, W));
+    CHK(ensure_track(ctx, B));
+    T.valid = false;                                     // a step that fails half way leaves no boxes behind
+    if (image_u8) {
+        const size_t nbytes = (size_t)B * H * W * 3;
+        if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int saved_prof = ctx->profiling;
+    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
+    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    const int cur = T.cur, nxt = T.cur ^ 1;
+    for (int b0 = 0; b0 < B; b0 += mb) {
+        const int nb = std::min(mb, B - b0);
+        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one step = one profile: keep the earlier chunks
+        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
+        const float* d_hs = hand_side + (size_t)b0 * 2;
+        const unsigned char* d_u8 = image_u8 ? ctx->d_u8 + (size_t)b0 * H * W * 3 : nullptr;
+        if (!dev) {
+            CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * 2, false));
+            d_hs = ctx->d_hs;
+            if (!image_u8) { CHK(copy_in(ctx, ctx->d_image, d_img, (size_t)nb * H * W * 3, false)); d_img = ctx->d_image; }
+        }
+        float* bc = T.center[cur] + (size_t)b0 * 2;
+        float* bs = T.scale[cur] + b0;
+        if (detect) {
+            if (image_u8) {
+                ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
+                preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
+                HIPCHK(ctx, hipGetLastError());
+                d_img = ctx->d_image;
+            }
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, image_u8 != nullptr, false));
+            {
+                ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
+                track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
+            }
+            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
+            crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
+        } else if (image_u8) {
+            ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
+            crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
+            ++ctx->crop_u8_launches;
+        } else {
+            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
+            crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        CHK(run_posenet(ctx, ctx->d_crop, nb, 256, 256, true));
+        float* kpmap_out = kp_scoremap ? kp_scoremap + (size_t)b0 * 256 * 256 * 21 : nullptr;
+        int32_t* kpc_out = kp_crop ? kp_crop + (size_t)b0 * 42 : nullptr;
+        double* kpi_out = kp_image ? kp_image + (size_t)b0 * 42 : nullptr;
+        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
+            if (kpmap_out) {
+                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * nb * (32 * 32 * 21 + 256 * 256 * 21));
+                resize_bilinear_launch(ctx->d_sm[2], nb, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
+            }
+            return 0;
+        };
+        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
+            CHK(run_kp_detect(ctx, nb, kpc_out, kpi_out, dev, bs, bc));
+            ProfScope ps(ctx, "track_box", "track_box", 0.0, 4.0 * nb * 32 * 32 * 21);
+            track_box_launch(dev && kpi_out ? kpi_out : ctx->d_kpimg, ctx->d_sm[2], 32, nb, H, W, 256, ctx->track_margin, ctx->track_min_score,
+                             ctx->track_use_min_score, T.center[nxt] + (size_t)b0 * 2, T.scale[nxt] + b0, T.conf + b0, T.lost + b0,
+                             detect ? nullptr : T.detected + b0, ctx->stream);
+            return 0;
+        };
+        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, nb, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+        auto off = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)nb * 256 * 256 * 3, dev));
+        CHK(copy_out(ctx, off(scale_crop, 1), bs, (size_t)nb, dev));
+        CHK(copy_out(ctx, off(center, 2), bc, (size_t)nb * 2, dev));
+        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)nb * 256 * 256 * 21, false));
+        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)nb * 63, dev));
+        CHK(copy_out(ctx, off(confidence, 1), T.conf + b0, (size_t)nb, dev));
+        CHK(copy_out(ctx, (float*)(lost ? lost + b0 : nullptr), (const float*)(T.lost + b0), (size_t)nb, dev));           // (int32: four bytes each, as copy_out counts)
+        CHK(copy_out(ctx, (float*)(detected ? detected + b0 : nullptr), (const float*)(T.detected + b0), (size_t)nb, dev));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(T.h_lost, T.lost, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(T.ev_lost, ctx->stream));
+    T.pending = true;
+    T.cur = nxt; T.valid = true; T.B = B; T.H = H; T.W = W;
+    T.since = detect ? 0 : T.since + 1;
+    ++(detect ? ctx->track_detect_steps : ctx->track_tracked_steps);
+    if (!dev) return finish_op(ctx);
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1781,6 +1966,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
     if (ctx->d_keys) hipFree(ctx->d_keys);
     if (ctx->d_det) hipFree(ctx->d_det);
     if (ctx->d_mgscratch) hipFree(ctx->d_mgscratch);
+    track_free(ctx);
     if (ctx->d_u8) hipFree(ctx->d_u8);
     if (ctx->blob16) hipFree(ctx->blob16);
     if (ctx->d_concat16) hipFree(ctx->d_concat16);
@@ -1916,6 +2102,23 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
         if (v == "1") HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "no hipGraph in the CPU interpreter build");
 #endif
         ctx->use_graph = v == "1";
+        return 0;
+    }
+    if (k == "track_margin" || k == "track_min_score") {
+        if (k == "track_min_score" && v == "off") { ctx->track_use_min_score = 0; return 0; }
+        char* end = nullptr;
+        const float f = strtof(value, &end);
+        if (end == value || *end || !(f == f) || (k == "track_margin" && !(f > 0.f && f <= 16.f)))
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "%s wants a number%s, got %s", key, k == "track_margin" ? " in (0, 16]" : " or \"off\"", value);
+        if (k == "track_margin") ctx->track_margin = f;
+        else { ctx->track_min_score = f; ctx->track_use_min_score = 1; }
+        return 0;
+    }
+    if (k == "track_redetect") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1 << 20)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_redetect wants a non-negative integer, got %s", value);
+        ctx->track_redetect = (int)n;
         return 0;
     }
     if (k == "micro_batch" && v == "auto") { ctx->micro_batch = -1; return 0; }
@@ -2177,6 +2380,102 @@ int hp3d_infer_full_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* im
                        float* center, float* keypoints_scoremap, float* keypoint_coord3d, float* hand_mask) {
     return infer_full_chunked(ctx, B, H, W, nullptr, hand_side, hand_scoremap, image_crop, scale_crop, center,
                               keypoints_scoremap, keypoint_coord3d, hand_mask, false, image_u8, Hin, Win);
+}
+
+// ---- tracking: hands across video frames ----------------------------------------------------------------
+int hp3d_track_reset(hp3d_ctx* ctx) {
+    if (!ctx) return HP3D_ERR_ARG;
+    ctx->track.valid = false;
+    ctx->track.since = 0;
+    return 0;
+}
+
+int hp3d_track_seed(hp3d_ctx* ctx, int B, int H, int W, const float* center, const float* scale) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!center || !scale) HP3D_FAIL(ctx, HP3D_ERR_ARG, "center / scale is NULL");
+    CHK(check_img(ctx, B, H, W));
+    for (int b = 0; b < B; ++b) {
+        if (!(scale[b] > 0.f) || !std::isfinite(scale[b])) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_seed: scale[%d] = %g must be positive and finite", b, (double)scale[b]);
+        if (!std::isfinite(center[b * 2]) || !std::isfinite(center[b * 2 + 1])) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_seed: center[%d] is not finite", b);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(ensure_track(ctx, B));
+    TrackState& T = ctx->track;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }
+    HIPCHK(ctx, hipMemcpyAsync(T.center[T.cur], center, sizeof(float) * (size_t)B * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(T.scale[T.cur], scale, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(T.lost, 0, sizeof(int) * (size_t)B, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < B; ++b) T.h_lost[b] = 0;
+    T.valid = true; T.B = B; T.H = H; T.W = W; T.since = 0;
+    return 0;
+}
+
+int hp3d_track_step(hp3d_ctx* ctx, int B, int H, int W, const float* image, const float* hand_side, float* image_crop,
+                    float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                    int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return track_step_impl(ctx, B, H, W, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false);
+}
+int hp3d_track_step_dev(hp3d_ctx* ctx, int B, int H, int W, const float* image, const float* hand_side, float* image_crop,
+                        float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                        int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return track_step_impl(ctx, B, H, W, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, true);
+}
+int hp3d_track_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, const float* hand_side,
+                       float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                       int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (Hin != H || Win != W)
+        HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "tracking crops straight from the uint8 frame: the frame (%dx%d) must have the network size (%dx%d)", Hin, Win, H, W);
+    return track_step_impl(ctx, B, H, W, nullptr, image_u8, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false);
+}
+
+int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw, const float* score32, float margin, float* center,
+                   float* scale, float* confidence, int32_t* lost) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!keypoint_hw || !center || !scale || !confidence || !lost || B < 1 || H < 1 || W < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (!(margin >= 0.f && margin <= 16.f)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_box: margin %g must be 0 (= option track_margin) or in (0, 16]", (double)margin);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    double* d_kp = S.upload(keypoint_hw, (size_t)B * 42); NN(ctx, d_kp);
+    float* d_sm = nullptr;
+    if (score32) { d_sm = S.upload(score32, (size_t)B * 32 * 32 * 21); NN(ctx, d_sm); }
+    float* d_c = S.alloc<float>((size_t)B * 2); NN(ctx, d_c);
+    float* d_s = S.alloc<float>(B); NN(ctx, d_s);
+    float* d_q = S.alloc<float>(B); NN(ctx, d_q);
+    int* d_l = S.alloc<int>(B); NN(ctx, d_l);
+    track_box_launch(d_kp, d_sm, 21, B, H, W, 256, margin > 0.f ? margin : ctx->track_margin, ctx->track_min_score, ctx->track_use_min_score, d_c, d_s, d_q, d_l,
+                     nullptr, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(center, d_c, sizeof(float) * (size_t)B * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(scale, d_s, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(confidence, d_q, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lost, d_l, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, const float* center,
+                            const float* scale, int crop_size, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image_u8 || !center || !scale || !out || B < 1 || H < 2 || W < 2 || crop_size < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t no = (size_t)B * crop_size * crop_size * 3;
+    unsigned char* d_x = S.upload(image_u8, (size_t)B * H * W * 3); NN(ctx, d_x);
+    float* d_c = S.upload(center, (size_t)B * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)B); NN(ctx, d_s);
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    crop_and_resize_u8_launch(d_x, B, H, W, d_c, d_s, crop_size, d_o, ctx->stream);
+    ++ctx->crop_u8_launches;
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
 }
 
 int hp3d_preprocess_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int Hin, int Win, int H, int W, float* out) {
@@ -2540,6 +2839,9 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"conv_wino_launches", &Counters::conv_wino_launches, true},
         {"conv_mfma_launches", &Counters::conv_mfma_launches, true},
         {"conv_splitk_reduce_launches", &Counters::conv_splitk_reduce_launches, true},
+        {"track_detect_steps", &Counters::track_detect_steps, false},
+        {"track_tracked_steps", &Counters::track_tracked_steps, false},
+        {"crop_u8_launches", &Counters::crop_u8_launches, false},
     };
     const std::string k(name);
     for (const auto& c : table)

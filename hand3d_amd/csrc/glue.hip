@@ -254,10 +254,22 @@ void preprocess_u8_kernel(const unsigned char* img, int B, int H, int W, int oh,
     }
 }
 
-// crop_image_from_xy -> tf.image.crop_and_resize (utils/general.py:163-196, App. B.4)
-HP3D_KERNEL(256)
-void crop_and_resize_kernel(const float* img, int B, int H, int W, int C, const float* center, const float* scale,
-                            int crop, float* out) {
+// crop_image_from_xy -> tf.image.crop_and_resize (utils/general.py:163-196, App. B.4).  One body for both pixel types: `tap(pixel, c)` is
+// the value of channel c of pixel `pixel` of the whole batch -- a float32 image as it is, a uint8 frame normalised as
+// preprocess_u8_kernel does at equal sizes (x / 255 - 0.5, float32 op by op), so that the crop straight from a uint8 frame equals
+// preprocess_u8 -> crop_and_resize bit for bit without the normalised float frame ever existing (25 MB at 1080x1920).  The
+// extrapolation value 0 is a normalised value.
+struct TapF32 {
+    const float* img; int C;
+    __device__ __forceinline__ float operator()(size_t pixel, int c) const { return img[pixel * C + c]; }
+};
+struct TapU8 {
+    const unsigned char* img; int C;
+    __device__ __forceinline__ float operator()(size_t pixel, int c) const { return (float)img[pixel * C + c] / 255.0f - 0.5f; }
+};
+template <class Tap>
+__device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H, int W, int C, const float* center, const float* scale,
+                                                     int crop, float* out) {
     const long total = (long)B * crop * crop;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % crop);
@@ -283,15 +295,25 @@ void crop_and_resize_kernel(const float* img, int B, int H, int W, int C, const 
         const int ty0 = (int)floorf(in_y), ty1 = (int)ceilf(in_y);
         const int tx0 = (int)floorf(in_x), tx1 = (int)ceilf(in_x);
         const float ly = in_y - (float)ty0, lx = in_x - (float)tx0;
-        const float* ib = img + (size_t)b * H * W * C;
+        const size_t ib = (size_t)b * H * W;
         for (int c = 0; c < C; ++c) {
-            const float tl = ib[((size_t)ty0 * W + tx0) * C + c], tr = ib[((size_t)ty0 * W + tx1) * C + c];
-            const float bl = ib[((size_t)ty1 * W + tx0) * C + c], br = ib[((size_t)ty1 * W + tx1) * C + c];
+            const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
+            const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
             const float top = tl + (tr - tl) * lx;
             const float bot = bl + (br - bl) * lx;
             o[c] = top + (bot - top) * ly;
         }
     }
+}
+HP3D_KERNEL(256)
+void crop_and_resize_kernel(const float* img, int B, int H, int W, int C, const float* center, const float* scale,
+                            int crop, float* out) {
+    crop_and_resize_body(TapF32{img, C}, B, H, W, C, center, scale, crop, out);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_u8_kernel(const unsigned char* img, int B, int H, int W, const float* center, const float* scale,
+                               int crop, float* out) {
+    crop_and_resize_body(TapU8{img, 3}, B, H, W, 3, center, scale, crop, out);
 }
 
 HP3D_KERNEL(256)
@@ -1059,6 +1081,93 @@ void kp_detect_kernel(const float* sm, int h, int w, int C, int cs, int oh, int 
     }
 }
 
+// ---- tracking ----------------------------------------------------------------------------------------
+// np.maximum / np.minimum: a NaN on either side is the result (fmaxf / fminf would drop it, and the rule below relies on it reaching
+// the "not finite -> 200" test)
+__device__ __forceinline__ float np_maximum(float a, float b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ float np_minimum(float a, float b) { return (a <= b || a != a) ? a : b; }
+__device__ __forceinline__ bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
+
+// The next frame's crop box from this frame's 21 image-space keypoints: the dataset readers' hand_crop rule
+// (data/BinaryDbReader.py:268-308, data/BinaryDbReaderSTB.py:219-259), float32 op by op in the reader's order, all 21 keypoints
+// "visible": centre = keypoint 12 ((0, 0) when not finite), size = 2 x the largest distance from the centre to the keypoints'
+// bounding box clamped to the frame, x margin, clamped to [50, 500] (not finite -> 200), scale = crop / size clamped to [1, 10].
+// margin = 1 is the reader's rule bit for bit; 1.25 is the factor the detection path puts on its own box (ColorHandPose3DNetwork.py:84).
+// One workgroup per image.  kp_image [B,21,2] float64 (row, col) as kp_detect_kernel writes it; sm (may be null) the last 32 x 32
+// score maps with channel stride cs: confidence = mean over the 21 channels (added in channel order) of each channel's maximum
+// (NaNs never win), 0 without a map.  lost = 1 when keypoint 12 is not finite or lies outside the frame (row < 0, row > H, col < 0,
+// col > W), or -- with a threshold and a map -- when the confidence is not at least the threshold.  detected0 (may be null): zeroed
+// for the image (a tracked step's "no box of this step came from HandSegNet").
+HP3D_KERNEL(256)
+void track_box_kernel(const double* kp_image, const float* sm, int cs, int H, int W, int crop, float margin, float min_score,
+                      int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0) {
+    __shared__ float cmax[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (sm) {
+        const int c = t & 31, g = t >> 5;
+        float m = -__builtin_inff();
+        if (c < 21) {
+            const float* xb = sm + (size_t)b * 1024 * cs + c;
+            for (int i = g; i < 1024; i += 8) {
+                const float v = xb[(size_t)i * cs];
+                m = v > m ? v : m;
+            }
+        }
+        cmax[t] = m;
+    }
+    __syncthreads();
+    if (t == 0) {
+        float conf = 0.f;
+        if (sm) {
+            float s = 0.f;
+            for (int c = 0; c < 21; ++c) {
+                float m = cmax[c];
+                for (int g = 1; g < 8; ++g) m = cmax[g * 32 + c] > m ? cmax[g * 32 + c] : m;
+                s = s + m;
+            }
+            conf = s / 21.0f;
+        }
+        const double* kp = kp_image + (size_t)b * 42;
+        const float r12 = (float)kp[24], c12 = (float)kp[25];
+        const bool cfin = finite_f32(r12) && finite_f32(c12);
+        const float cy = cfin ? r12 : 0.f, cx = cfin ? c12 : 0.f;
+        float mn0 = (float)kp[0], mn1 = (float)kp[1], mx0 = mn0, mx1 = mn1;
+        for (int k = 1; k < 21; ++k) {
+            const float r = (float)kp[k * 2], c = (float)kp[k * 2 + 1];
+            mn0 = np_minimum(mn0, r); mn1 = np_minimum(mn1, c);
+            mx0 = np_maximum(mx0, r); mx1 = np_maximum(mx1, c);
+        }
+        mn0 = np_maximum(mn0, 0.f); mn1 = np_maximum(mn1, 0.f);
+        mx0 = np_minimum(mx0, (float)H); mx1 = np_minimum(mx1, (float)W);
+        const float b0 = 2.f * np_maximum(mx0 - cy, cy - mn0), b1 = 2.f * np_maximum(mx1 - cx, cx - mn1);
+        float best = np_maximum(b0, b1);
+        best = best * margin;
+        best = np_minimum(np_maximum(best, 50.f), 500.f);
+        if (!finite_f32(best)) best = 200.f;
+        center[b * 2] = cy; center[b * 2 + 1] = cx;
+        scale[b] = np_minimum(np_maximum((float)crop / best, 1.f), 10.f);
+        confidence[b] = conf;
+        lost[b] = (!cfin || r12 < 0.f || r12 > (float)H || c12 < 0.f || c12 > (float)W ||
+                   (use_min_score && sm && !(conf >= min_score))) ? 1 : 0;
+        if (detected0) detected0[b] = 0;
+    }
+}
+
+// A detect step's choice per image: an image whose previous box was lost (or every image, force_all) takes HandSegNet's box,
+// the others keep the tracked one.  detected[b] = 1 where HandSegNet's was taken.
+HP3D_KERNEL(256)
+void track_select_kernel(const int* lost_prev, const float* det_center, const float* det_scale, int B, int force_all,
+                         float* box_center, float* box_scale, int* detected) {
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+        const int d = (force_all || lost_prev[b] != 0) ? 1 : 0;
+        if (d) {
+            box_center[b * 2] = det_center[b * 2]; box_center[b * 2 + 1] = det_center[b * 2 + 1];
+            box_scale[b] = det_scale[b];
+        }
+        detected[b] = d;
+    }
+}
+
 inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
     long g = (total + block - 1) / block;
     if (g < 1) g = 1;
@@ -1223,6 +1332,21 @@ void bone_rel_inv_launch(const float* rel, int B, float* xyz, hipStream_t s) {
 void kp_detect_launch(const float* sm, int B, int h, int w, int C, int cs, int oh, int ow, const float* scale,
                       const float* center, int* kp_crop, double* kp_image, hipStream_t s) {
     HP3D_LAUNCH(kp_detect_kernel, dim3(C, B), dim3(256), 0, s, sm, h, w, C, cs, oh, ow, scale, center, kp_crop, kp_image);
+}
+void crop_and_resize_u8_launch(const unsigned char* img, int B, int H, int W, const float* center, const float* scale, int crop,
+                               float* out, hipStream_t s) {
+    HP3D_LAUNCH(crop_and_resize_u8_kernel, dim3(grid_for((long)B * crop * crop)), dim3(256), 0, s, img, B, H, W, center, scale,
+                crop, out);
+}
+void track_box_launch(const double* kp_image, const float* sm, int cs, int B, int H, int W, int crop, float margin, float min_score,
+                      int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0, hipStream_t s) {
+    HP3D_LAUNCH(track_box_kernel, dim3(B), dim3(256), 0, s, kp_image, sm, cs, H, W, crop, margin, min_score, use_min_score, center,
+                scale, confidence, lost, detected0);
+}
+void track_select_launch(const int* lost_prev, const float* det_center, const float* det_scale, int B, int force_all,
+                         float* box_center, float* box_scale, int* detected, hipStream_t s) {
+    HP3D_LAUNCH(track_select_kernel, dim3(grid_for(B)), dim3(256), 0, s, lost_prev, det_center, det_scale, B, force_all, box_center,
+                box_scale, detected);
 }
 void argmax2d_launch(const float* x, int B, int H, int W, int C, int cs, int* out_rc, hipStream_t s) {
     HP3D_LAUNCH(argmax2d_kernel, dim3(C, B), dim3(256), 0, s, x, H, W, C, cs, out_rc);

@@ -429,6 +429,15 @@ void bone_rel_inv_launch(const float* rel, int B, float* xyz, hipStream_t s);   
 // first arg-max of the up-sampled (oh x ow, legacy bilinear) score map per channel + trafo_coords; h*w <= 4096
 void kp_detect_launch(const float* sm, int B, int h, int w, int C, int cs, int oh, int ow, const float* scale,
                       const float* center, int* kp_crop, double* kp_image, hipStream_t s);
+// tracking: the crop straight from a uint8 frame [B,H,W,3] (= preprocess_u8 at equal sizes -> crop_and_resize, bit for bit);
+// the next crop box from the keypoints kp_detect wrote (+ confidence from the 32 x 32 score maps `sm`, channel stride cs, may be null;
+// detected0, may be null, is zeroed); a detect step's per-image choice between HandSegNet's box and the tracked one
+void crop_and_resize_u8_launch(const unsigned char* img, int B, int H, int W, const float* center, const float* scale, int crop,
+                               float* out, hipStream_t s);
+void track_box_launch(const double* kp_image, const float* sm, int cs, int B, int H, int W, int crop, float margin, float min_score,
+                      int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0, hipStream_t s);
+void track_select_launch(const int* lost_prev, const float* det_center, const float* det_scale, int B, int force_all,
+                         float* box_center, float* box_scale, int* detected, hipStream_t s);
 void argmax2d_launch(const float* x, int B, int H, int W, int C, int cs, int* out_rc, hipStream_t s);
 void copy_channels_launch(const float* in, int npix, int C, int in_cs, float* out, int out_cs, hipStream_t s);
 size_t mask_grow_lds_bytes(int H, int W);

@@ -135,6 +135,24 @@ class ColorHandPose3DNetwork(object):
         o = self.engine.infer_full(image, hand_side, outputs=('coord3d', 'kp_crop', 'kp_hw', 'scale', 'center'))
         return o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center']
 
+    def track(self, image, hand_side):
+        """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
+            call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
+            HandSegNet as inference() does; every other call crops with the box the dataset readers' hand_crop rule
+            (data/BinaryDbReader.py:268-308) derives from the previous call's keypoints and runs no HandSegNet at all.
+            `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3] (tracked steps then crop straight from the uint8 frame).
+            Returns what inference_keypoints() returns -- keypoint_coord3d, keypoint_hw, keypoint_hw_crop, scale_crop, center (the
+            box this step used) -- plus confidence [B], lost [B] (1: the next step will detect again) and detected [B]
+            (1: this step's box came from HandSegNet). """
+        step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
+        o = step(image, hand_side)
+        return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],
+                o['detected'])
+
+    def track_reset(self):
+        """ The next track() call detects the hand anew (a cut in the video, another hand). """
+        self.engine.track_reset()
+
     def inference2d_keypoints(self, image):
         """ inference2d() + detect_keypoints + trafo_coords on the device (eval2d.py:58,93-94): keypoint_hw [B,21,2]
             float64 in the input image, keypoint_hw_crop [B,21,2] float64, scale_crop, center. """

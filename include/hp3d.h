@@ -146,6 +146,12 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            images ("0" = never split; default "auto" = at most 32 in float32 mode -- fewer when H x W x 64 floats x N
  *                            would pass 2^31 bytes, e.g. 480x640: balanced chunks of <= 27 -- and no split with f16 trunks).
  *                            Bit-identical to making the calls chunk by chunk;
+ *          "track_margin"  = "1.25" (default) | a number in (0, 16]: the factor hp3d_track_step* / hp3d_track_box put on the box size
+ *                            the readers' rule gives ("1" = that rule bit for bit).  1.25 is what the detection path puts on its own box
+ *                            (ColorHandPose3DNetwork.py:84): a policy choice for the hand's motion between frames, not a measurement;
+ *          "track_min_score" = "off" (default) | a number: a tracked image counts as lost when its confidence is below it.  A useful
+ *                            value depends on the trained weights: callers calibrate it on the confidence the steps return;
+ *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image;
  *          "f16_impl"     = "h16" (default) | "mfma" | "h16_force": with half-precision trunks (hp3d_finalize_weights dtype 1),
  *                            the 3x3 / stride-1 layers with Cin >= 64 run on the half-precision trunk kernel (conv_h16.hip)
  *                            whenever their grid fills the chip | never (general kernel only) | whenever the shape allows
@@ -265,6 +271,57 @@ int hp3d_poseprior(hp3d_ctx* ctx, int B, int variant, const float* scoremap256, 
 int hp3d_pose3d(hp3d_ctx* ctx, int B, const float* scoremap32, const float* hand_side,
                 float* coord_xyz_rel_normed, float* coord_can, float* rot_mat);
 
+/* ---- tracking: a hand across video frames -------------------------------------
+ * The whole-path calls above treat every frame as a single picture (ColorHandPose3DNetwork.inference, :61-99): HandSegNet over the
+ * whole frame, mask, box, crop, then PoseNet2D and the lifting stage.  On frame t + 1 of a video the 21 keypoints of frame t already
+ * say where the hand is.  A tracking step crops with the box the dataset readers' hand_crop rule derives from keypoints
+ * (data/BinaryDbReader.py:268-308, data/BinaryDbReaderSTB.py:219-259 -- the crops PoseNet2D was trained on and
+ * eval2d_gt_cropped.py evaluates it on): centre = keypoint 12, size = 2 x the largest distance from the centre to the keypoints'
+ * bounding box, x option "track_margin", clamped to [50, 500], scale = 256 / size clamped to [1, 10] -- applied to the PREVIOUS
+ * step's predicted keypoints, and runs no HandSegNet, soft-max or mask growth ("tracked step").  A "detect step" runs them for the
+ * whole batch as hp3d_infer_full does and then, per image, keeps the tracked box where the previous step did not flag it as lost.
+ * A step detects: the first time after hp3d_create / hp3d_track_reset / a change of (B, H, W); when the previous step flagged ANY
+ * image as lost (the whole batch detects: one kernel plan per step, no gather); and, with option "track_redetect" = N > 0, every
+ * N-th step (a scheduled re-detection takes HandSegNet's box for every image).  The decision is taken on the host from the previous
+ * step's flags before anything is enqueued; a tracked step needs no HandSegNet weights.
+ * hp3d_track_reset    the next step detects.
+ * hp3d_track_seed     start from boxes the caller has (another detector, ground truth): center [B,2] (row, col) finite, scale [B] > 0;
+ *                     the next step for (B, H, W) is a tracked step.
+ * hp3d_track_step     image [B,H,W,3] (x/255-0.5 done by the caller), hand_side [B,2] -> image_crop [B,256,256,3], scale_crop [B,1] and
+ *                     center [B,2] (the boxes THIS step cropped with), keypoints_scoremap [B,256,256,21] (may be NULL like any output),
+ *                     keypoint_coord3d [B,21,3], keypoint_hw_crop [B,21,2] int32 and keypoint_hw [B,21,2] float64 (detect_keypoints /
+ *                     trafo_coords as in hp3d_infer_full_kp), confidence [B] = the mean over the 21 channels of the maximum of
+ *                     PoseNet2D's last 32x32 score map, lost [B] int32 = 1 where the NEXT box is unusable (keypoint 12 not finite or
+ *                     outside the frame: row < 0, row > H, col < 0, col > W; or confidence below option "track_min_score"),
+ *                     detected [B] int32 = 1 where this step's box came from HandSegNet.  hand_scoremap / hand_mask are not outputs.
+ * hp3d_track_step_dev the same on device pointers, stream-ordered; the flags also travel to a page-locked buffer of the context and
+ *                     the next step waits for that copy before it decides -- the only wait tracking adds.
+ * hp3d_track_step_u8  uint8 frames [B,Hin,Win,3] on the host; Hin x Win must equal H x W (HP3D_ERR_UNSUPPORTED otherwise): a tracked
+ *                     step crops straight from the uint8 frame and never builds the normalised float frame; a detect step
+ *                     normalises it first as hp3d_infer_full_u8 does.
+ * Batches above the micro-batch limit run chunk by chunk on one stream; half-precision trunks work; no graph replay.
+ * hp3d_track_box (per-op) the box rule alone: keypoint_hw [B,21,2] float64 (row, col), score32 [B,32,32,21] or NULL (confidence 0,
+ *                     no threshold test), margin = the factor on the size (0: option "track_margin") -> center [B,2], scale [B],
+ *                     confidence [B], lost [B]; uses option "track_min_score"; with margin = 1 it is the readers' rule bit for bit.
+ * hp3d_crop_and_resize_u8 (per-op) crop_image_from_xy (utils/general.py:163-196) straight from uint8 frames [B,H,W,3]: every tap is
+ *                     normalised (x/255-0.5, data/BinaryDbReader.py:182) and interpolated; bit-identical to hp3d_preprocess_u8 at
+ *                     equal sizes followed by hp3d_crop_and_resize.                                                           */
+int hp3d_track_reset(hp3d_ctx* ctx);
+int hp3d_track_seed(hp3d_ctx* ctx, int B, int H, int W, const float* center, const float* scale);
+int hp3d_track_step(hp3d_ctx* ctx, int B, int H, int W, const float* image, const float* hand_side, float* image_crop,
+                    float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                    int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected);
+int hp3d_track_step_dev(hp3d_ctx* ctx, int B, int H, int W, const float* image, const float* hand_side, float* image_crop,
+                        float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                        int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected);
+int hp3d_track_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, const float* hand_side,
+                       float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                       int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected);
+int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw, const float* score32, float margin, float* center,
+                   float* scale, float* confidence, int32_t* lost);
+int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, const float* center,
+                            const float* scale, int crop_size, float* out);
+
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65
  *                      x [B,H,W,Cin], w HWIO, SAME padding incl. the asymmetric stride-2 case.
@@ -327,6 +384,8 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "conv_wino7_launches" = 7x7 layers that ran on conv_wino7.hip (option "wino7"), "conv_wino7_split_launches" = those of them in the channel-split form; "conv_pw2_launches" = 1x1 layer pairs that ran as one launch (option "pw2");
  * "first_touch_launches" = read passes in front of conv1_1 (option "first_touch");
  * "mask_grow_global_launches" = mask growths (one launch per call or chunk, all its images) on the global-scratch kernel (option "mask_grow");
+ * "track_detect_steps" / "track_tracked_steps" = hp3d_track_step* calls that ran HandSegNet / that cropped from the previous step's keypoints;
+ * "crop_u8_launches" = crops taken straight from a uint8 frame (hp3d_track_step_u8's tracked steps, one per chunk; hp3d_crop_and_resize_u8);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);

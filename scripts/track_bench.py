@@ -1,0 +1,135 @@
+"""Tracked steps against the full path: hp3d_infer_full_kp_dev and tracked steps of hp3d_track_step_dev on the same
+context and device-resident frames, in one process; warm-up, then the median of three timed regions, as bench.py does.  Also the
+B = 1 uint8 host-frame calls at 1080x1920 (hp3d_infer_full_kp_u8 / hp3d_track_step_u8 and the float32 host step).  The yardstick for
+a tracked step is the same run's full-path time minus its event-timed HandSegNet stage and soft-max + mask-growth rows: what the
+step would cost if skipping were free.  Tracked steps are timed twice: as a video runs them (seeded once, then step after step;
+valid only if the counters say that every timed step was a tracked one -- with random weights a step may lose the hand) and with
+hp3d_track_seed in front of every step (always tracked; the seed's two uploads and stream synchronise are timed on their own as
+well).  Writes one JSON line to profiles/track_bench.json."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from hand3d_amd import _lib, synth      # noqa: E402
+
+
+def median3(fn, steps, sync):
+    ts = []
+    for _ in range(3):
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        sync()
+        ts.append((time.perf_counter() - t0) / steps * 1e3)
+    return sorted(ts)[1]
+
+
+def case(e, B, H, W, steps, warmup):
+    img = synth.make_batch(B, B, H, W)
+    hs = synth.hand_sides(B)
+    d_img, d_hs = e.to_device(img), e.to_device(hs)
+    out = {k: e.dev_alloc(n) for k, n in (('coord3d', B * 63 * 4), ('kp_hw', B * 42 * 8), ('kp_crop', B * 42 * 4), ('center', B * 8),
+                                          ('scale', B * 4), ('confidence', B * 4), ('lost', B * 4), ('detected', B * 4))}
+    full = lambda: e.infer_full_dev(B, H, W, d_img, d_hs, coord3d=out['coord3d'], kp_crop=out['kp_crop'], kp_hw=out['kp_hw'],
+                                    center=out['center'], scale=out['scale'])
+    step = lambda: e.track_step_dev(B, H, W, d_img, d_hs, **{k: int(v) for k, v in out.items()})
+    # seed with the full path's own boxes: every timed step is a tracked one whatever random-weight keypoints say
+    o = e.infer_full(img, hs, outputs=('scale', 'center'))
+
+    seed = lambda: e.track_seed(o['center'], o['scale'], H, W)
+
+    def tracked():
+        seed()
+        step()
+    for _ in range(warmup):
+        full(); tracked()
+    r = {'B': B, 'H': H, 'W': W}
+    r['full_ms'] = median3(full, steps, e.sync)
+    n0 = e.counter('track_tracked_steps')
+    r['tracked_seeded_ms'] = median3(tracked, steps, e.sync)
+    assert e.counter('track_tracked_steps') - n0 == 3 * steps, "a timed step was not a tracked one"
+    r['seed_only_ms'] = median3(seed, steps, e.sync)
+    # as a video runs it: seeded once, then step after step on the device's own boxes
+    seed()
+    n0 = e.counter('track_tracked_steps')
+    unseeded = median3(step, steps, e.sync)
+    r['tracked_unseeded_all_tracked'] = e.counter('track_tracked_steps') - n0 == 3 * steps
+    r['tracked_unseeded_ms'] = unseeded if r['tracked_unseeded_all_tracked'] else None
+    r['tracked_ms'] = r['tracked_unseeded_ms'] if r['tracked_unseeded_all_tracked'] else r['tracked_seeded_ms']
+    e.set_profiling(1)
+    full(); e.sync()
+    t = e.get_timing()
+    glue = sum(ms for name, _, ms, _, _ in e.profile() if name in ('seg_upsample_softmax', 'mask_grow'))
+    step_rows = None
+    tracked(); e.sync()
+    step_rows = {name: round(ms, 4) for name, _, ms, _, _ in e.profile() if not name.startswith(('PoseNet2D/', 'PosePrior', 'ViewpointNet/', 'fc'))}
+    tt = e.get_timing()
+    e.set_profiling(0)
+    r['full_stage_ms'] = {k: round(v, 4) for k, v in t.items()}
+    r['tracked_stage_ms'] = {k: round(v, 4) for k, v in tt.items()}
+    r['tracked_glue_rows_ms'] = step_rows
+    r['softmax_maskgrow_ms'] = round(glue, 4)
+    r['yardstick_ms'] = r['full_ms'] - t['HandSegNet'] - glue
+    r['tracked_over_yardstick'] = r['tracked_ms'] / r['yardstick_ms']
+    r['full_over_tracked'] = r['full_ms'] / r['tracked_ms']
+    for b in list(out.values()) + [d_img, d_hs]:
+        b.free()
+    return r
+
+
+def host_u8_case(e, H, W, steps, warmup):
+    img = synth.make_batch(3, 1, H, W)
+    u8 = np.clip(np.rint((img + 0.5) * 255.0), 0, 255).astype(np.uint8)
+    hs = synth.hand_sides(1)
+    o = e.infer_full(img, hs, outputs=('scale', 'center'))
+    kpc, kph, c3 = np.empty((1, 21, 2), np.int32), np.empty((1, 21, 2), np.float64), np.empty((1, 21, 3), np.float32)
+    p = _lib._ptr
+
+    def full_u8():
+        e._chk(e.lib.hp3d_infer_full_kp_u8(e.h, 1, H, W, p(u8), H, W, p(hs), None, None, None, None, None, p(c3), None, p(kpc), p(kph)))
+    lost, det, conf = np.empty(1, np.int32), np.empty(1, np.int32), np.empty(1, np.float32)
+
+    def tracked_u8():
+        e.track_seed(o['center'], o['scale'], H, W)
+        e._chk(e.lib.hp3d_track_step_u8(e.h, 1, H, W, p(u8), H, W, p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+
+    def tracked_f32():
+        e.track_seed(o['center'], o['scale'], H, W)
+        e._chk(e.lib.hp3d_track_step(e.h, 1, H, W, p(img), p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+    for _ in range(warmup):
+        full_u8(); tracked_u8(); tracked_f32()
+    return {'H': H, 'W': W, 'full_u8_host_ms': median3(full_u8, steps, e.sync), 'tracked_u8_host_ms': median3(tracked_u8, steps, e.sync),
+            'tracked_f32_host_ms': median3(tracked_f32, steps, e.sync)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'track_bench.json'))
+    a = ap.parse_args()
+    e = _lib.Engine(0)
+    e.load_weight_dict(synth.make_weights())
+    e.finalize_weights(0)
+    res = {'bench': 'track', 'steps': a.steps, 'warmup': a.warmup,
+           'cases': [case(e, 1, 240, 320, a.steps, a.warmup), case(e, 1, 1080, 1920, max(a.steps // 2, 5), a.warmup),
+                     case(e, 32, 320, 320, max(a.steps // 2, 5), max(a.warmup // 2, 2))],
+           'host_u8_1080p': host_u8_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup)}
+    e.close()
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(line + '\n')
+    print(line)
+
+
+if __name__ == '__main__':
+    main()
