@@ -3,6 +3,7 @@
 
     python examples/run.py img1.png img2.png ...          (needs ./weights/*.pickle, like the reference)
     python examples/run.py --synthetic                    (seeded synthetic weights + images)
+    python examples/run.py --synthetic --hands 2          (up to K hands per image from one HandSegNet pass: one line per hand found)
 """
 import json
 import tempfile
@@ -14,6 +15,7 @@ from common import parser, synthetic_weight_files
 if __name__ == '__main__':
     ap = parser(__doc__)
     ap.add_argument('images', nargs='*')
+    ap.add_argument('--hands', type=int, default=1, help="up to K hands per image (1 ... 4; default 1: the reference's output)")
     a = ap.parse_args()
     from hand3d_amd import synth
     from hand3d_amd.nets.ColorHandPose3DNetwork import ColorHandPose3DNetwork
@@ -31,6 +33,15 @@ if __name__ == '__main__':
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                 # run.py:40: left hand
     for i, image_raw in enumerate(frames):
         image_v = np.expand_dims((image_raw.astype('float') / 255.0) - 0.5, 0)                       # run.py:59
+        if a.hands > 1:          # every slot as a left hand, like run.py:40
+            _, _, scale_k, center_k, _, coord3d_k, valid, area, kp_hw = \
+                net.inference_hands(image_v, np.tile(hand_side_v, (1, a.hands, 1)), a.hands)
+            for k in range(a.hands):
+                if valid[0, k]:
+                    print(json.dumps({'image': i, 'hand': k, 'area': int(area[0, k]), 'center': center_k[0, k].tolist(),
+                                      'scale': float(scale_k[0, k]), 'wrist_hw': kp_hw[0, k, 0].tolist(),
+                                      'wrist_xyz': coord3d_k[0, k, 0].tolist()}))
+            continue
         hand_scoremap_v, image_crop_v, scale_v, center_v, keypoints_scoremap_v, keypoint_coord3d_v = \
             net.inference(image_v, hand_side_v, True)                                                  # run.py:61-64
         keypoint_coord3d_v = np.squeeze(keypoint_coord3d_v)

@@ -59,6 +59,10 @@ _SIGNATURES = {
     'hp3d_resize_bilinear': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_crop_and_resize': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p]),
+    'hp3d_infer_hands': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13),
+    'hp3d_infer_hands_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13),
+    'hp3d_infer_hands_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    'hp3d_masks_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7),
     'hp3d_track_reset': (C.c_int, [_ctx]),
     'hp3d_track_seed': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'hp3d_track_step': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
@@ -91,6 +95,7 @@ _SIGNATURES = {
     'hp3d_crc32c': (C.c_uint32, [C.c_void_p, C.c_size_t]),
 }
 COMM_ID_BYTES = 128
+MAX_HANDS = 4               # HP3D_MAX_HANDS
 TIMING_STAGES = ('HandSegNet', 'mask_crop', 'PoseNet2D', 'lifting', 'total')
 EXPORTS = tuple(sorted(_SIGNATURES))
 
@@ -318,6 +323,71 @@ class Engine(object):
         else:
             self._chk(self.lib.hp3d_infer_full_dev(self.h, B, H, W, v(image_ptr), v(hand_side_ptr), v(scoremap), v(crop),
                                                    v(scale), v(center), v(kpmap), v(coord3d), v(mask)))
+
+    # -- several hands per frame (include/hp3d.h) ---------------------------------------
+    _HANDS_ORDER = ('scoremap', 'crop', 'scale', 'center', 'kpmap', 'coord3d', 'mask', 'kp_crop', 'kp_hw', 'valid', 'area')
+    _HANDS_DEFAULT = ('scoremap', 'crop', 'scale', 'center', 'kpmap', 'coord3d', 'kp_crop', 'kp_hw')
+
+    @staticmethod
+    def _hands_outputs(B, K, H, W, want_mask, outputs):
+        want = lambda k: k in outputs
+        return {'scoremap': np.empty((B, H, W, 2), np.float32) if want('scoremap') else None,
+                'crop': np.empty((B, K, 256, 256, 3), np.float32) if want('crop') else None,
+                'scale': np.empty((B, K), np.float32) if want('scale') else None,
+                'center': np.empty((B, K, 2), np.float32) if want('center') else None,
+                'kpmap': np.empty((B, K, 256, 256, 21), np.float32) if want('kpmap') else None,
+                'coord3d': np.empty((B, K, 21, 3), np.float32) if want('coord3d') else None,
+                'mask': np.empty((B, K, H, W), np.float32) if want_mask else None,
+                'kp_crop': np.empty((B, K, 21, 2), np.int32) if want('kp_crop') else None,
+                'kp_hw': np.empty((B, K, 21, 2), np.float64) if want('kp_hw') else None,
+                'valid': np.empty((B, K), np.int32), 'area': np.empty((B, K), np.int32)}
+
+    def infer_hands(self, image, hand_side, max_hands, want_mask=False, outputs=_HANDS_DEFAULT):
+        """Up to max_hands hands per frame from one HandSegNet pass: image [B,H,W,3], hand_side [B,K,2] (per slot).  Returns a dict with
+        infer_full's outputs on an extra K axis ([B,K,...]; scoremap stays [B,H,W,2]) plus valid [B,K] and area [B,K]; slots without a
+        hand have valid = 0 and run on the fall-back crop."""
+        image, hand_side = _f32(image), _f32(hand_side)
+        assert image.ndim == 4 and image.shape[3] == 3, "image must be [B,H,W,3]"
+        B, H, W, _ = image.shape
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._hands_outputs(B, K, H, W, want_mask, outputs)
+        self._chk(self.lib.hp3d_infer_hands(self.h, B, H, W, K, _ptr(image), _ptr(hand_side), *[_ptr(o[k]) for k in self._HANDS_ORDER]))
+        return o
+
+    def infer_hands_u8(self, image_u8, hand_side, max_hands, H=240, W=320, want_mask=False, outputs=_HANDS_DEFAULT):
+        """infer_hands on uint8 frames [B,Hin,Win,3]: normalised and resized to H x W on the device."""
+        img = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        hand_side = _f32(hand_side)
+        assert img.ndim == 4 and img.shape[3] == 3, "image must be [B,Hin,Win,3] uint8"
+        B, Hin, Win, _ = img.shape
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._hands_outputs(B, K, H, W, want_mask, outputs)
+        self._chk(self.lib.hp3d_infer_hands_u8(self.h, B, Hin, Win, _ptr(img), int(H), int(W), K, _ptr(hand_side),
+                                               *[_ptr(o[k]) for k in self._HANDS_ORDER]))
+        return o
+
+    def infer_hands_dev(self, B, H, W, K, image_ptr, hand_side_ptr, scoremap=0, crop=0, scale=0, center=0, kpmap=0, coord3d=0, mask=0,
+                        kp_crop=0, kp_hw=0, valid=0, area=0):
+        """Device-pointer variant (ints); stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_infer_hands_dev(self.h, B, H, W, K, v(image_ptr), v(hand_side_ptr), v(scoremap), v(crop), v(scale),
+                                                v(center), v(kpmap), v(coord3d), v(mask), v(kp_crop), v(kp_hw), v(valid), v(area)))
+
+    def masks_from_scoremap(self, scoremap, max_hands):
+        """The mask stage of infer_hands alone: scoremap [B,H,W,2] -> dict of mask [B,K,H,W], center [B,K,2], crop_size [B,K],
+        scale [B,K], seed int32 [B,K,2], valid [B,K], area [B,K]."""
+        sm = _f32(scoremap)
+        B, H, W, c2 = sm.shape
+        assert c2 == 2
+        K = int(max_hands)
+        o = {'mask': np.empty((B, K, H, W), np.float32), 'center': np.empty((B, K, 2), np.float32),
+             'crop_size': np.empty((B, K), np.float32), 'scale': np.empty((B, K), np.float32),
+             'seed': np.empty((B, K, 2), np.int32), 'valid': np.empty((B, K), np.int32), 'area': np.empty((B, K), np.int32)}
+        self._chk(self.lib.hp3d_masks_from_scoremap(self.h, _ptr(sm), B, H, W, K,
+                                                    *[_ptr(o[k]) for k in ('mask', 'center', 'crop_size', 'scale', 'seed', 'valid', 'area')]))
+        return o
 
     # -- tracking: a hand across video frames (include/hp3d.h, DESIGN.md 4.11) -------------------------
     def track_reset(self):

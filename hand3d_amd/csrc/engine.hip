@@ -279,6 +279,7 @@ struct Options {
     float track_min_score = 0.f;    // option "track_min_score": a tracked image is lost when its confidence is below this ...
     int track_use_min_score = 0;    // ... "off" (default): never
     int track_redetect = 0;         // option "track_redetect": every N-th tracking step is a detect step that re-boxes every image (0: never)
+    int hands_min_area = 0;         // option "hands_min_area": hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer pixels (0: off)
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -303,6 +304,7 @@ struct Counters {
     long conv_mfma_launches = 0;                    // layers that went to the general direct kernel (conv_mfma.hip, f32 and f16)
     long conv_splitk_reduce_launches = 0;           // channel-split reduces (conv_splitk_reduce*_launch)
     long mask_grow_global_launches = 0;             // mask growths on the global-scratch kernel
+    long mask_grow_multi_launches = 0;              // mask growths of the multi-hand kernels (either form)
     long track_detect_steps = 0, track_tracked_steps = 0;      // hp3d_track_step*: steps that ran HandSegNet / that did not
     long crop_u8_launches = 0;                      // crops taken straight from a uint8 frame (crop_and_resize_u8_kernel)
 };
@@ -362,6 +364,8 @@ struct hp3d_ctx : Options, Counters {
     size_t gather_floats = 0;
     int comm_rank = 0, comm_size = 1;
     int* d_seed = nullptr;
+    int *d_valid = nullptr, *d_area = nullptr;      // hp3d_infer_hands*: per slot
+    size_t mask_floats = 0;                         // capacity of d_mask
     unsigned long long* d_keys = nullptr;
     unsigned char* d_det = nullptr;
     unsigned char* d_u8 = nullptr;
@@ -522,8 +526,10 @@ bool mask_grow_global(const hp3d_ctx* ctx, int H, int W) {
 }
 
 // ---- arena ---------------------------------------------------------------------------------
-int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
-    const size_t px = (size_t)B * std::max((size_t)H * W, (size_t)256 * 256);
+// B images of H x W; `slots` (>= B; 0 = B) crops behind them: the multi-hand calls run K crops per image
+int ensure_arena(hp3d_ctx* ctx, int B, int H, int W, int slots = 0) {
+    slots = std::max(slots, B);
+    const size_t px = std::max((size_t)B * std::max((size_t)H * W, (size_t)256 * 256), (size_t)slots * 256 * 256);
     const size_t act = px * 64;
     if (act > ctx->act_floats) {
         CHK(dev_realloc(ctx, &ctx->bufA, act));
@@ -539,6 +545,7 @@ int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
     if (largef > ctx->large_floats) {
         CHK(dev_realloc(ctx, &ctx->d_large, largef));
         CHK(dev_realloc(ctx, &ctx->d_mask, (size_t)B * H * W));
+        ctx->mask_floats = (size_t)B * H * W;
         CHK(dev_realloc(ctx, &ctx->d_fg, (size_t)B * H * W));
         CHK(dev_realloc(ctx, &ctx->d_segsmall, (size_t)B * (H / 8 + 1) * (W / 8 + 1) * 32));
         ctx->large_floats = largef;
@@ -551,7 +558,8 @@ int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
         CHK(dev_realloc(ctx, &ctx->d_mgscratch, (size_t)B * mask_grow_global_words(H, W)));
         ctx->mg_words = (size_t)B * mask_grow_global_words(H, W);
     }
-    if (B > ctx->capB) {
+    if (slots > ctx->capB) {
+        B = slots;
         CHK(dev_realloc(ctx, &ctx->d_hs, (size_t)B * 2));
         CHK(dev_realloc(ctx, &ctx->d_crop, (size_t)B * 256 * 256 * 3));
         CHK(dev_realloc(ctx, &ctx->d_center, (size_t)B * 2));
@@ -569,6 +577,8 @@ int ensure_arena(hp3d_ctx* ctx, int B, int H, int W) {
         CHK(dev_realloc(ctx, &ctx->d_fc2, (size_t)B * 512));
         CHK(dev_realloc(ctx, &ctx->d_fcpart, std::max((size_t)B * 17 * 512 + (size_t)B * 33 * 256, (size_t)B * 16 * 18 * 256)));      // (FC slices; conv_s2_gemm: 18 slices x 16 B rows x 256)
         CHK(dev_realloc(ctx, &ctx->d_seed, (size_t)B * 2));
+        CHK(dev_realloc(ctx, &ctx->d_valid, (size_t)B));
+        CHK(dev_realloc(ctx, &ctx->d_area, (size_t)B));
         CHK(dev_realloc(ctx, &ctx->d_keys, (size_t)B));
         ctx->capB = B;
         ctx->sideB = B;
@@ -1372,12 +1382,30 @@ int copy_out(hp3d_ctx* ctx, float* dst, const float* src, size_t n, bool dev) {
 }
 
 // stages 2-8 of the full path on device-resident image/hand_side
-int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W, int want_mask, bool image_hot = false, bool do_crop = true) {
+// K > 0: the multi-hand form -- HandSegNet once, the soft-max also writes fg, up to K hands per image into slots
+// b * K + j of d_center / d_scale / d_cropsize / d_seed / d_valid / d_area (/ d_mask), and B * K crops from the B frames
+int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W, int want_mask, bool image_hot = false, bool do_crop = true,
+                        int K = 0) {
     CHK(run_handsegnet(ctx, d_image, B, H, W, image_hot));
-    MaskBuffers mb{ctx->d_keys, ctx->d_det, nullptr};
+    MaskBuffers mb{ctx->d_keys, ctx->d_det, K > 0 ? ctx->d_fg : nullptr};
     {
         ProfScope ps(ctx, "seg_upsample_softmax", "seg_upsample_softmax", 0.0, 4.0 * B * H * W * 2 + (double)B * H * W);
         seg_upsample_softmax_launch(ctx->d_segsmall, B, H / 8, W / 8, 32, H, W, ctx->d_large, mb, ctx->stream);
+    }
+    if (K > 0) {
+        {
+            ProfScope ps(ctx, "mask_grow_multi", "mask_grow_multi", 0.0, (double)B * H * W * 5);
+            const bool global = mask_grow_global(ctx, H, W);
+            mask_grow_multi_launch(mb, B, H, W, K, ctx->hands_min_area, ctx->empty_fltmax, global ? ctx->d_mgscratch : nullptr,
+                                   want_mask ? ctx->d_mask : nullptr, ctx->d_center, ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->d_valid,
+                                   ctx->d_area, ctx->stream);
+            ++ctx->mask_grow_multi_launches;
+            if (global) ++ctx->mask_grow_global_launches;
+        }
+        ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * B * (H * W * 3 + K * 256 * 256 * 3));
+        crop_and_resize_launch(d_image, B * K, H, W, 3, ctx->d_center, ctx->d_scale, 256, ctx->d_crop, ctx->stream, K);
+        HIPCHK(ctx, hipGetLastError());
+        return 0;
     }
     {
         ProfScope ps(ctx, "mask_grow", "mask_grow", 0.0, (double)B * H * W);
@@ -1816,6 +1844,81 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     return 0;
 }
 
+// Up to K hands per frame: HandSegNet, the soft-max and ONE multi-hand mask growth per chunk of frames, then the back
+// half of infer_full_impl -- PoseNet2D, the lifting towers with the heat-map up-sampling and the keypoint detection beside them -- at
+// batch nb * K with per-slot centre / scale / hand_side.  No compaction: absent slots run on their fall-back crop, so a call has one
+// kernel plan and no host wait.  A chunk holds at most micro_batch / K frames: no launch behind the crop sees more slots than a
+// single-hand call's chunk has images.  One stream, no graph replay.
+int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, int Hin, int Win,
+                     const float* hand_side, float* hand_scoremap, float* image_crop, float* scale_crop, float* center, float* kp_scoremap,
+                     float* coord3d, float* hand_mask, int32_t* kp_crop, double* kp_image, int32_t* valid, int32_t* area, bool dev) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    if (image_u8 && (Hin < 2 || Win < 2)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad uint8 frame size %dx%d", Hin, Win);
+    CHK(check_img(ctx, B, H, W));
+    CHK(need_nets(ctx, NET_SEG | NET_POSE | NET_PRIOR | NET_VP));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int front = auto_micro_batch(ctx, B, H, W), back = auto_micro_batch(ctx, B * K, 256, 256);
+    int mb = front <= 0 ? B : std::min(front, B);
+    if (back > 0) mb = std::min(mb, std::max(1, back / K));
+    CHK(ensure_arena(ctx, mb, H, W, mb * K));
+    if (hand_mask && (size_t)mb * K * H * W > ctx->mask_floats) {
+        CHK(dev_realloc(ctx, &ctx->d_mask, (size_t)mb * K * H * W));
+        ctx->mask_floats = (size_t)mb * K * H * W;
+    }
+    const int saved_prof = ctx->profiling;
+    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
+    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    for (int b0 = 0; b0 < B; b0 += mb) {
+        const int nb = std::min(mb, B - b0), ns = nb * K;
+        const size_t s0 = (size_t)b0 * K;
+        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one call = one profile: keep the earlier chunks
+        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
+        const float* d_hs = hand_side + s0 * 2;
+        if (image_u8) {
+            const size_t nbytes = (size_t)nb * Hin * Win * 3;
+            if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8 + (size_t)b0 * Hin * Win * 3, nbytes, hipMemcpyHostToDevice, ctx->stream));
+            preprocess_u8_launch(ctx->d_u8, nb, Hin, Win, H, W, ctx->d_image, ctx->stream);
+            d_img = ctx->d_image;
+        } else if (!dev) {
+            CHK(copy_in(ctx, ctx->d_image, d_img, (size_t)nb * H * W * 3, false));
+            d_img = ctx->d_image;
+        }
+        if (!dev) { CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false)); d_hs = ctx->d_hs; }
+        CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, true, K));
+        CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
+        float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
+        int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
+        double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
+        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
+            if (kpmap_out) {
+                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
+                resize_bilinear_launch(ctx->d_sm[2], ns, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
+            }
+            return 0;
+        };
+        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
+            if (kpc_out || kpi_out) CHK(run_kp_detect(ctx, ns, kpc_out, kpi_out, dev));
+            return 0;
+        };
+        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        CHK(copy_out(ctx, hand_scoremap ? hand_scoremap + (size_t)b0 * H * W * 2 : nullptr, ctx->d_large, (size_t)nb * H * W * 2, dev));
+        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
+        CHK(copy_out(ctx, off(scale_crop, 1), ctx->d_scale, (size_t)ns, dev));
+        CHK(copy_out(ctx, off(center, 2), ctx->d_center, (size_t)ns * 2, dev));
+        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
+        CHK(copy_out(ctx, off(hand_mask, (size_t)H * W), ctx->d_mask, (size_t)ns * H * W, dev));
+        CHK(copy_out(ctx, (float*)(valid ? valid + s0 : nullptr), (const float*)ctx->d_valid, (size_t)ns, dev));           // (int32: four bytes each, as copy_out counts)
+        CHK(copy_out(ctx, (float*)(area ? area + s0 : nullptr), (const float*)ctx->d_area, (size_t)ns, dev));
+    }
+    if (!dev) return finish_op(ctx);
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1959,6 +2062,8 @@ int hp3d_destroy(hp3d_ctx* ctx) {
 #endif
     if (ctx->comm) hp3d_comm_destroy(ctx);
     if (ctx->d_seed) hipFree(ctx->d_seed);
+    if (ctx->d_valid) hipFree(ctx->d_valid);
+    if (ctx->d_area) hipFree(ctx->d_area);
     if (ctx->d_liftbar) hipFree(ctx->d_liftbar);
 #ifndef HP3D_EMU
     if (ctx->h_lifterr) hipHostFree(ctx->h_lifterr);
@@ -2112,6 +2217,13 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
             HP3D_FAIL(ctx, HP3D_ERR_ARG, "%s wants a number%s, got %s", key, k == "track_margin" ? " in (0, 16]" : " or \"off\"", value);
         if (k == "track_margin") ctx->track_margin = f;
         else { ctx->track_min_score = f; ctx->track_use_min_score = 1; }
+        return 0;
+    }
+    if (k == "hands_min_area") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1L << 30)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "hands_min_area wants a non-negative integer (0 = off), got %s", value);
+        ctx->hands_min_area = (int)n;
         return 0;
     }
     if (k == "track_redetect") {
@@ -2380,6 +2492,75 @@ int hp3d_infer_full_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* im
                        float* center, float* keypoints_scoremap, float* keypoint_coord3d, float* hand_mask) {
     return infer_full_chunked(ctx, B, H, W, nullptr, hand_side, hand_scoremap, image_crop, scale_crop, center,
                               keypoints_scoremap, keypoint_coord3d, hand_mask, false, image_u8, Hin, Win);
+}
+
+// ---- several hands per frame ------------------------------------------------------------------------------
+int hp3d_infer_hands(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* hand_scoremap,
+                     float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                     float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return infer_hands_impl(ctx, B, H, W, K, image, nullptr, 0, 0, hand_side, hand_scoremap, image_crop, scale_crop, center,
+                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, false);
+}
+int hp3d_infer_hands_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* hand_scoremap,
+                         float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                         float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return infer_hands_impl(ctx, B, H, W, K, image, nullptr, 0, 0, hand_side, hand_scoremap, image_crop, scale_crop, center,
+                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, true);
+}
+int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
+                        float* hand_scoremap, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                        float* keypoint_coord3d, float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid,
+                        int32_t* area) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return infer_hands_impl(ctx, B, H, W, K, nullptr, image_u8, Hin, Win, hand_side, hand_scoremap, image_crop, scale_crop, center,
+                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, false);
+}
+
+int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, float* mask, float* center,
+                             float* crop_size, float* scale, int32_t* seed, int32_t* valid, int32_t* area) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!scoremap || B < 1 || H < 1 || W < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    if (!(B < H && B < W)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "Scoremap must be [Batch, Width, Height]");  // general.py:210
+    if ((long)H * W > (1L << 30)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "map too large (more than 2^30 pixels)");
+    const bool global = mask_grow_global(ctx, H, W);
+    if (!global && !mask_grow_lds_fits(H, W)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "map too large for the in-LDS mask growth");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t npx = (size_t)B * H * W, ns = (size_t)B * K;
+    float* d_sm = S.upload(scoremap, npx * 2); NN(ctx, d_sm);
+    MaskBuffers mb;
+    mb.argmax_key = S.alloc<unsigned long long>(B); NN(ctx, mb.argmax_key);
+    mb.det = S.alloc<unsigned char>(npx); NN(ctx, mb.det);
+    mb.fg = S.alloc<float>(npx); NN(ctx, mb.fg);
+    float* d_mask = nullptr;
+    if (mask) { d_mask = S.alloc<float>(ns * H * W); NN(ctx, d_mask); }
+    float* d_c = S.alloc<float>(ns * 2); NN(ctx, d_c);
+    float* d_cs = S.alloc<float>(ns); NN(ctx, d_cs);
+    float* d_sc = S.alloc<float>(ns); NN(ctx, d_sc);
+    int* d_seed = S.alloc<int>(ns * 2); NN(ctx, d_seed);
+    int* d_valid = S.alloc<int>(ns); NN(ctx, d_valid);
+    int* d_area = S.alloc<int>(ns); NN(ctx, d_area);
+    unsigned* d_scr = nullptr;
+    if (global) { d_scr = S.alloc<unsigned>((size_t)B * mask_grow_global_words(H, W)); NN(ctx, d_scr); }
+    seg_softmax_launch(d_sm, B, H, W, mb, ctx->stream);
+    mask_grow_multi_launch(mb, B, H, W, K, ctx->hands_min_area, ctx->empty_fltmax, d_scr, d_mask, d_c, d_cs, d_sc, d_seed, d_valid, d_area,
+                           ctx->stream);
+    ++ctx->mask_grow_multi_launches;
+    if (global) ++ctx->mask_grow_global_launches;
+    if (mask) HIPCHK(ctx, hipMemcpyAsync(mask, d_mask, ns * H * W * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (center) HIPCHK(ctx, hipMemcpyAsync(center, d_c, sizeof(float) * ns * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (crop_size) HIPCHK(ctx, hipMemcpyAsync(crop_size, d_cs, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (scale) HIPCHK(ctx, hipMemcpyAsync(scale, d_sc, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (seed) HIPCHK(ctx, hipMemcpyAsync(seed, d_seed, sizeof(int) * ns * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (valid) HIPCHK(ctx, hipMemcpyAsync(valid, d_valid, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (area) HIPCHK(ctx, hipMemcpyAsync(area, d_area, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
 }
 
 // ---- tracking: hands across video frames ----------------------------------------------------------------
@@ -2821,6 +3002,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"graph_replays", &Counters::graph_replays, false},
         {"lift_overlap_calls", &Counters::lift_overlap_calls, false},
         {"mask_grow_global_launches", &Counters::mask_grow_global_launches, true},
+        {"mask_grow_multi_launches", &Counters::mask_grow_multi_launches, false},
         {"conv_h16_launches", &Counters::conv_h16_launches, true},
         {"conv_h16_first_resident_launches", &Counters::conv_h16_first_resident_launches, true},
         {"first_touch_launches", &Counters::first_touch_launches, true},

@@ -269,7 +269,7 @@ struct TapU8 {
 };
 template <class Tap>
 __device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H, int W, int C, const float* center, const float* scale,
-                                                     int crop, float* out) {
+                                                     int crop, float* out, int boxes_per_image) {
     const long total = (long)B * crop * crop;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % crop);
@@ -295,7 +295,8 @@ __device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H
         const int ty0 = (int)floorf(in_y), ty1 = (int)ceilf(in_y);
         const int tx0 = (int)floorf(in_x), tx1 = (int)ceilf(in_x);
         const float ly = in_y - (float)ty0, lx = in_x - (float)tx0;
-        const size_t ib = (size_t)b * H * W;
+        // box b crops image b / boxes_per_image (the K hands of a frame come from the one frame)
+        const size_t ib = (size_t)(boxes_per_image == 1 ? b : b / boxes_per_image) * H * W;
         for (int c = 0; c < C; ++c) {
             const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
             const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
@@ -307,13 +308,13 @@ __device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H
 }
 HP3D_KERNEL(256)
 void crop_and_resize_kernel(const float* img, int B, int H, int W, int C, const float* center, const float* scale,
-                            int crop, float* out) {
-    crop_and_resize_body(TapF32{img, C}, B, H, W, C, center, scale, crop, out);
+                            int crop, float* out, int boxes_per_image) {
+    crop_and_resize_body(TapF32{img, C}, B, H, W, C, center, scale, crop, out, boxes_per_image);
 }
 HP3D_KERNEL(256)
 void crop_and_resize_u8_kernel(const unsigned char* img, int B, int H, int W, const float* center, const float* scale,
-                               int crop, float* out) {
-    crop_and_resize_body(TapU8{img, 3}, B, H, W, 3, center, scale, crop, out);
+                               int crop, float* out, int boxes_per_image) {
+    crop_and_resize_body(TapU8{img, 3}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
 }
 
 HP3D_KERNEL(256)
@@ -750,6 +751,325 @@ void mask_grow_global_kernel(const unsigned long long* keys, int H, int W, int e
     }
     mask_grow_epilogue(obj, P, b, H, W, s_box[cur][0], s_box[cur][1], s_box[cur][2], s_box[cur][3], sy, sx, empty_fltmax, mask_out,
                        center, crop_size, scale, seed_out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Up to K hands per image.  R_0 = det; a growth runs inside R from the first arg-max of fg over R's pixels and is then
+// taken out of R (R &= ~O), so the objects are pairwise disjoint; an object of at least min_area pixels becomes the next hand, in the
+// order of discovery; at most 4 K growths per image.  Slot j of image b is index b * K + j of every output.  The first seed is the image's
+// global arg-max (keys): it lies in det unless det is empty, and then slot 0 is what the single-hand kernels give (empty mask, fall-back
+// box) with valid = 0.  Slots that stay without a hand: valid = 0, area = 0, zero mask, seed (-1, -1), the fall-back box.
+// The two kernels stand beside the single-hand ones (same passes, same bits for slot 0) instead of sharing their loop bodies, so that the
+// single-hand path compiles to what it compiled to before.
+//
+// u64 maximum over the workgroup, returned to every thread.  Every thread calls it.
+__device__ __forceinline__ unsigned long long block_max_u64_all(unsigned long long v) {
+    __shared__ unsigned long long s_red[16];
+    v = wave_max_u64(v);
+    const int wave = threadIdx.x >> 6, nwave = (blockDim.x + 63) >> 6;
+    __syncthreads();                     // (the previous call's readers are done with s_red)
+    if ((threadIdx.x & 63) == 0) s_red[wave] = v;
+    __syncthreads();
+    for (int i = 0; i < nwave; ++i) v = s_red[i] > v ? s_red[i] : v;
+    return v;
+}
+
+// the key (softmax_det_key's) of the first arg-max of fg over the set bits of the packed map R (pitch P); 0: R is empty
+__device__ __forceinline__ unsigned long long mask_argmax_in(const unsigned* R, const float* fg, int W, int P, int NWORD) {
+    unsigned long long best = 0ull;
+    for (int w = threadIdx.x; w < NWORD; w += blockDim.x) {
+        unsigned v = R[w];
+        if (v) {
+            const int y = w / P, wx = w - y * P;
+            const unsigned base = (unsigned)y * (unsigned)W + (unsigned)wx * 32u;
+            while (v) {
+                const unsigned idx = base + (unsigned)(__ffs(v) - 1);
+                v &= v - 1u;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(fg[idx]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+                best = key > best ? key : best;
+            }
+        }
+    }
+    return block_max_u64_all(best);
+}
+
+// slots j0 .. K-1 of image b hold no hand.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void mask_absent_slots(int b, int j0, int K, int H, int W, int empty_fltmax, float* mask_out, float* center,
+                                                  float* crop_size, float* scale, int* seed_out, int* valid, int* area) {
+    for (int j = j0; j < K; ++j) {
+        const int slot = b * K + j;
+        if (mask_out) {
+            float* mo = mask_out + (size_t)slot * H * W;
+            for (int i = threadIdx.x; i < H * W; i += blockDim.x) mo[i] = 0.f;
+        }
+        mask_grow_epilogue(nullptr, 0, slot, H, W, 0x7fffffff, -1, 0x7fffffff, -1, -1, -1, empty_fltmax, nullptr, center, crop_size, scale,
+                           seed_out);
+        if (threadIdx.x == 0) { valid[slot] = 0; area[slot] = 0; }
+    }
+}
+
+HP3D_KERNEL(1024)
+void mask_grow_multi_kernel(const unsigned char* det, const float* fg, const unsigned long long* keys, int H, int W, int K, int min_area,
+                            int empty_fltmax, float* mask_out, float* center, float* crop_size, float* scale, int* seed_out,
+                            int* valid, int* area) {
+    HP3D_DYN_SMEM(smem_f);
+    const int WW = (W + 31) >> 5, P = WW + 1;
+    const int NWORD = H * P;
+    unsigned* detb = (unsigned*)smem_f;          // R: the part of det no object has taken yet
+    unsigned* obj = detb + NWORD + 1;
+    unsigned* tmp = obj + NWORD + 1;
+    __shared__ int s_changed[2], s_rmin, s_rmax, s_cmin, s_cmax, s_area;
+
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const unsigned char* d = det + (size_t)b * H * W;
+    const float* f = fg + (size_t)b * H * W;
+    const unsigned idx0 = 0xFFFFFFFFu - (unsigned)(keys[b] & 0xFFFFFFFFull);
+    int sy = (int)(idx0 / (unsigned)W), sx = (int)(idx0 % (unsigned)W);
+
+    for (int w = tid; w < NWORD; w += nthr) {
+        const int y = w / P, wx = w - y * P;
+        detb[w] = pack_det_word(d, y, wx, W, WW);
+    }
+    if (tid == 0) { obj[-1] = 0u; obj[NWORD] = 0u; }
+    __syncthreads();
+    // det is empty (the global arg-max lies outside it): slot 0 is the single-hand kernel's result
+    const bool legacy = !((unsigned)sy < (unsigned)H && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+
+    const int nseg = (H + MG_R - 1) / MG_R, nunits = nseg * WW;
+    const int num_passes = max(H, W) / 10;   // max(s[1], s[2]) // (filter_size // 2)
+    int k = 0, tries = 0;
+    for (;;) {
+        for (int w = tid; w < NWORD; w += nthr) {
+            const int y = w / P, wx = w - y * P;
+            obj[w] = (y == sy && wx == (sx >> 5)) ? (1u << (sx & 31)) : 0u;
+        }
+        if (tid == 0) { s_rmin = 0x7fffffff; s_rmax = -1; s_cmin = 0x7fffffff; s_cmax = -1; s_area = 0; s_changed[0] = s_changed[1] = 0; }
+        __syncthreads();
+        for (int pass = 0; pass < num_passes; ++pass) {         // the passes of mask_grow_kernel, inside R
+            for (int w = tid; w < NWORD; w += nthr) {
+                const unsigned long long lo = obj[w - 1], mid = obj[w], hi = obj[w + 1];
+                unsigned long long win = (mid << 16) | (lo >> 16) | (hi << 48);
+                win = win | (win << 1) | (win >> 1);     // radius 1
+                win = win | (win << 2) | (win >> 2);     // radius 3
+                win = win | (win << 4) | (win >> 4);     // radius 7
+                win = win | (win << 3) | (win >> 3);     // radius 10
+                tmp[w] = (unsigned)(win >> 16);
+            }
+            __syncthreads();
+            if (tid == 0) s_changed[(pass + 1) & 1] = 0;
+            int changed = 0;
+            for (int u = tid; u < nunits; u += nthr) {
+                const int seg = u / WW, wx = u - seg * WW;
+                const int y0 = seg * MG_R;
+                unsigned v[MG_R + 20];
+                const int base = (y0 - 10) * P + wx;
+#pragma unroll
+                for (int i = 0; i < MG_R + 20; ++i) {
+                    const bool ok = (unsigned)(y0 - 10 + i) < (unsigned)H;
+                    const unsigned r = tmp[ok ? base + i * P : wx];
+                    v[i] = ok ? r : 0u;
+                }
+                unsigned a2[MG_R + 17], a4[MG_R + 5];
+                {
+                    unsigned a1[MG_R + 19];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 19; ++i) a1[i] = v[i] | v[i + 1];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 17; ++i) a2[i] = a1[i] | a1[i + 2];
+                    unsigned a3[MG_R + 13];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 13; ++i) a3[i] = a2[i] | a2[i + 4];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 5; ++i) a4[i] = a3[i] | a3[i + 8];
+                }
+#pragma unroll
+                for (int j = 0; j < MG_R; ++j) {
+                    const int y = y0 + j;
+                    if (y < H) {
+                        const int w = y * P + wx;
+                        const unsigned acc = (a4[j] | a2[j + 16] | v[j + 20]) & detb[w];     // rows y-10 .. y+10
+                        if (acc != obj[w]) changed = 1;
+                        obj[w] = acc;
+                    }
+                }
+            }
+            if (changed) s_changed[pass & 1] = 1;
+            __syncthreads();
+            if (!s_changed[pass & 1]) break;
+        }
+        // bounding box and pixel count of the object
+        int rmin = 0x7fffffff, rmax = -1, cmin = 0x7fffffff, cmax = -1, cnt = 0;
+        for (int w = tid; w < NWORD; w += nthr) {
+            const unsigned v = obj[w];
+            if (v) {
+                const int y = w / P, wx = w - y * P;
+                rmin = min(rmin, y); rmax = max(rmax, y);
+                cmin = min(cmin, wx * 32 + (__ffs(v) - 1));
+                cmax = max(cmax, wx * 32 + (31 - __clz(v)));
+                cnt += __builtin_popcount(v);
+            }
+        }
+        if (rmax >= 0) {
+            atomicMin(&s_rmin, rmin); atomicMax(&s_rmax, rmax);
+            atomicMin(&s_cmin, cmin); atomicMax(&s_cmax, cmax);
+            atomicAdd(&s_area, cnt);
+        }
+        __syncthreads();
+        const int obj_area = s_area;
+        const bool accept = legacy || obj_area >= min_area;
+        if (accept) {
+            const int slot = b * K + k;
+            mask_grow_epilogue(obj, P, slot, H, W, s_rmin, s_rmax, s_cmin, s_cmax, sy, sx, empty_fltmax, mask_out, center, crop_size, scale,
+                               seed_out);
+            if (tid == 0) { valid[slot] = legacy ? 0 : 1; area[slot] = obj_area; }
+            ++k;
+        }
+        for (int w = tid; w < NWORD; w += nthr) detb[w] &= ~obj[w];
+        ++tries;
+        if (legacy || k == K || tries == 4 * K) break;
+        __syncthreads();        // R is final; the box and obj have been read
+        const unsigned long long key = mask_argmax_in(detb, f, W, P, NWORD);
+        if (!key) break;        // nothing left
+        const unsigned idx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+        sy = (int)(idx / (unsigned)W); sx = (int)(idx % (unsigned)W);
+    }
+    mask_absent_slots(b, k, K, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area);
+}
+
+// The same on the per-image scratch block of mask_grow_global_kernel (mask_pack_kernel has filled det and set the first seed).  The
+// active window restarts at each seed: a finished object is taken out of R and cleared from obj on its own bounding box, so obj is zero
+// outside the new seed again and the exactness argument above holds per growth (rows of tmp outside the window are never read).
+HP3D_KERNEL(1024)
+void mask_grow_multi_global_kernel(const float* fg, const unsigned long long* keys, int H, int W, int K, int min_area, int empty_fltmax,
+                                   unsigned* scratch, float* mask_out, float* center, float* crop_size, float* scale, int* seed_out,
+                                   int* valid, int* area) {
+    const int WW = (W + 31) >> 5, P = WW + 1;
+    const int NWORD = H * P;
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    unsigned* detb = scratch + (size_t)b * (3 * (size_t)NWORD + 2);      // R
+    unsigned* obj = detb + NWORD + 1;
+    unsigned* tmp = obj + NWORD + 1;
+    const float* f = fg + (size_t)b * H * W;
+    __shared__ int s_box[2][4], s_changed[2], s_area;
+    const unsigned idx0 = 0xFFFFFFFFu - (unsigned)(keys[b] & 0xFFFFFFFFull);
+    int sy = (int)(idx0 / (unsigned)W), sx = (int)(idx0 % (unsigned)W);
+    const bool seed_ok = (unsigned)sy < (unsigned)H;
+    const bool legacy = !(seed_ok && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+
+    const int num_passes = max(H, W) / 10;   // max(s[1], s[2]) // (filter_size // 2)
+    int k = 0, tries = 0;
+    for (;;) {
+        if (tid == 0) {
+            s_box[0][0] = s_box[0][1] = sy; s_box[0][2] = s_box[0][3] = sx;     // O_0 = {seed}
+            if (!seed_ok) s_box[0][1] = -1;
+            else obj[sy * P + (sx >> 5)] = 1u << (sx & 31);
+            s_changed[0] = s_changed[1] = 0; s_area = 0;
+        }
+        __syncthreads();
+        int cur = 0;                             // s_box[cur] = the box of what obj holds
+        for (int pass = 0; pass < num_passes; ++pass) {         // the passes of mask_grow_global_kernel, inside R
+            const int r0 = s_box[cur][0], r1 = s_box[cur][1], c0 = s_box[cur][2], c1 = s_box[cur][3];
+            if (tid == 0) { s_box[cur ^ 1][0] = 0x7fffffff; s_box[cur ^ 1][1] = -1; s_box[cur ^ 1][2] = 0x7fffffff; s_box[cur ^ 1][3] = -1; }
+            if (r1 < 0) break;
+            const int R0 = max(r0 - 10, 0), R1 = min(r1 + 10, H - 1);
+            const int wx0 = max(c0 - 10, 0) >> 5, wx1 = min(c1 + 10, W - 1) >> 5, nwx = wx1 - wx0 + 1;
+            const int nh = (r1 - r0 + 1) * nwx;
+            for (int i = tid; i < nh; i += nthr) {
+                const int yy = i / nwx, w = (r0 + yy) * P + wx0 + (i - yy * nwx);
+                const unsigned long long lo = obj[w - 1], mid = obj[w], hi = obj[w + 1];
+                unsigned long long win = (mid << 16) | (lo >> 16) | (hi << 48);
+                win = win | (win << 1) | (win >> 1);     // radius 1
+                win = win | (win << 2) | (win >> 2);     // radius 3
+                win = win | (win << 4) | (win >> 4);     // radius 7
+                win = win | (win << 3) | (win >> 3);     // radius 10
+                tmp[w] = (unsigned)(win >> 16);
+            }
+            __syncthreads();
+            if (tid == 0) s_changed[(pass + 1) & 1] = 0;
+            int changed = 0;
+            int rmin = 0x7fffffff, rmax = -1, cmin = 0x7fffffff, cmax = -1;
+            const int nunits = ((R1 - R0 + MG_R) / MG_R) * nwx;
+            for (int u = tid; u < nunits; u += nthr) {
+                const int seg = u / nwx, wx = wx0 + (u - seg * nwx);
+                const int y0 = R0 + seg * MG_R;
+                unsigned v[MG_R + 20];
+                const int base = (y0 - 10) * P + wx;
+#pragma unroll
+                for (int i = 0; i < MG_R + 20; ++i) {
+                    const int y = y0 - 10 + i;
+                    v[i] = (y >= r0 && y <= r1) ? tmp[base + i * P] : 0u;
+                }
+                unsigned a2[MG_R + 17], a4[MG_R + 5];
+                {
+                    unsigned a1[MG_R + 19];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 19; ++i) a1[i] = v[i] | v[i + 1];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 17; ++i) a2[i] = a1[i] | a1[i + 2];
+                    unsigned a3[MG_R + 13];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 13; ++i) a3[i] = a2[i] | a2[i + 4];
+#pragma unroll
+                    for (int i = 0; i < MG_R + 5; ++i) a4[i] = a3[i] | a3[i + 8];
+                }
+#pragma unroll
+                for (int j = 0; j < MG_R; ++j) {
+                    const int y = y0 + j;
+                    if (y <= R1) {
+                        const int w = y * P + wx;
+                        const unsigned acc = (a4[j] | a2[j + 16] | v[j + 20]) & detb[w];     // rows y-10 .. y+10
+                        if (acc != obj[w]) changed = 1;
+                        obj[w] = acc;
+                        if (acc) {
+                            rmin = min(rmin, y); rmax = max(rmax, y);
+                            cmin = min(cmin, wx * 32 + (__ffs(acc) - 1));
+                            cmax = max(cmax, wx * 32 + (31 - __clz(acc)));
+                        }
+                    }
+                }
+            }
+            if (rmax >= 0) {
+                atomicMin(&s_box[cur ^ 1][0], rmin); atomicMax(&s_box[cur ^ 1][1], rmax);
+                atomicMin(&s_box[cur ^ 1][2], cmin); atomicMax(&s_box[cur ^ 1][3], cmax);
+            }
+            if (changed) s_changed[pass & 1] = 1;
+            __syncthreads();
+            cur ^= 1;
+            if (!s_changed[pass & 1]) break;
+        }
+        // pixel count over the object's box (obj is zero outside it)
+        const int r0 = s_box[cur][0], r1 = s_box[cur][1], c0 = s_box[cur][2], c1 = s_box[cur][3];
+        const int bw0 = r1 >= 0 ? (c0 >> 5) : 0, nbw = r1 >= 0 ? (c1 >> 5) - bw0 + 1 : 0, nbox = r1 >= 0 ? (r1 - r0 + 1) * nbw : 0;
+        int cnt = 0;
+        for (int i = tid; i < nbox; i += nthr) {
+            const int yy = i / nbw;
+            cnt += __builtin_popcount(obj[(r0 + yy) * P + bw0 + (i - yy * nbw)]);
+        }
+        if (cnt) atomicAdd(&s_area, cnt);
+        __syncthreads();
+        const int obj_area = s_area;
+        const bool accept = legacy || obj_area >= min_area;
+        if (accept) {
+            const int slot = b * K + k;
+            mask_grow_epilogue(obj, P, slot, H, W, r0, r1, c0, c1, sy, sx, empty_fltmax, mask_out, center, crop_size, scale, seed_out);
+            if (tid == 0) { valid[slot] = legacy ? 0 : 1; area[slot] = obj_area; }
+            ++k;
+        }
+        __syncthreads();        // the mask has been read from obj
+        for (int i = tid; i < nbox; i += nthr) {
+            const int yy = i / nbw, w = (r0 + yy) * P + bw0 + (i - yy * nbw);
+            detb[w] &= ~obj[w];
+            obj[w] = 0u;
+        }
+        ++tries;
+        if (legacy || k == K || tries == 4 * K) break;
+        __syncthreads();        // R is final, obj is zero
+        const unsigned long long key = mask_argmax_in(detb, f, W, P, NWORD);
+        if (!key) break;        // nothing left
+        const unsigned idx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+        sy = (int)(idx / (unsigned)W); sx = (int)(idx % (unsigned)W);
+    }
+    mask_absent_slots(b, k, K, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1226,9 +1546,9 @@ void preprocess_u8_launch(const unsigned char* img, int B, int H, int W, int oh,
     HP3D_LAUNCH(preprocess_u8_kernel, dim3(grid_for((long)B * oh * ow * 3)), dim3(256), 0, s, img, B, H, W, oh, ow, out);
 }
 void crop_and_resize_launch(const float* img, int B, int H, int W, int C, const float* center, const float* scale,
-                            int crop, float* out, hipStream_t s) {
+                            int crop, float* out, hipStream_t s, int boxes_per_image) {
     HP3D_LAUNCH(crop_and_resize_kernel, dim3(grid_for((long)B * crop * crop)), dim3(256), 0, s, img, B, H, W, C,
-                center, scale, crop, out);
+                center, scale, crop, out, boxes_per_image);
 }
 // Streams `n` floats through the caches and keeps nothing (the store below never executes for finite data): what it leaves behind is
 // the buffer resident in the memory-side cache for the gather loads of the kernel that follows (option "first_touch").
@@ -1293,6 +1613,26 @@ void mask_grow_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltm
     HP3D_LAUNCH(mask_grow_kernel, dim3(B), dim3(1024), smem, s, (const unsigned char*)mb.det,
                 (const unsigned long long*)mb.argmax_key, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed);
 }
+// B images, K slots each: outputs at index b * K + j.  scratch: null = the LDS kernel, else B x mask_grow_global_words(H, W) words
+void mask_grow_multi_launch(const MaskBuffers& mb, int B, int H, int W, int K, int min_area, int empty_fltmax, unsigned* scratch,
+                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s) {
+    if (scratch) {
+        const long nword = (long)H * ((W + 31) / 32 + 1);
+        HP3D_LAUNCH(mask_pack_kernel, dim3(grid_for(nword, 256, 64), B), dim3(256), 0, s, (const unsigned char*)mb.det,
+                    (const unsigned long long*)mb.argmax_key, H, W, scratch);
+        HP3D_LAUNCH(mask_grow_multi_global_kernel, dim3(B), dim3(1024), 0, s, (const float*)mb.fg, (const unsigned long long*)mb.argmax_key,
+                    H, W, K, min_area, empty_fltmax, scratch, mask_out, center, crop_size, scale, seed, valid, area);
+        return;
+    }
+    const size_t smem = mask_grow_lds_bytes(H, W);
+    static bool attr_done[64] = {};
+    if (hp3d_first_use_on_device(attr_done))
+        // (dynamic + static LDS must stay within 160 KB: the kernel's own statics -- flags, box, the arg-max's per-wave keys -- take under
+        //  256 bytes, and mask_grow_lds_fits admits maps of at most 160 KB - 1 KB)
+        (void)hipFuncSetAttribute((const void*)mask_grow_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+    HP3D_LAUNCH(mask_grow_multi_kernel, dim3(B), dim3(1024), smem, s, (const unsigned char*)mb.det, (const float*)mb.fg,
+                (const unsigned long long*)mb.argmax_key, H, W, K, min_area, empty_fltmax, mask_out, center, crop_size, scale, seed, valid, area);
+}
 size_t fc_scratch_floats(int B, int Cin, int Cout) { return (size_t)((Cin + FC_KCH - 1) / FC_KCH) * B * Cout; }
 void fc_launch(const float* x, int B, int Cin, int x_stride, const float* w, const float* bias, int Cout, int act,
                float* out, int out_stride, float* scratch, hipStream_t s, const float* x2, int F1) {
@@ -1334,9 +1674,9 @@ void kp_detect_launch(const float* sm, int B, int h, int w, int C, int cs, int o
     HP3D_LAUNCH(kp_detect_kernel, dim3(C, B), dim3(256), 0, s, sm, h, w, C, cs, oh, ow, scale, center, kp_crop, kp_image);
 }
 void crop_and_resize_u8_launch(const unsigned char* img, int B, int H, int W, const float* center, const float* scale, int crop,
-                               float* out, hipStream_t s) {
+                               float* out, hipStream_t s, int boxes_per_image) {
     HP3D_LAUNCH(crop_and_resize_u8_kernel, dim3(grid_for((long)B * crop * crop)), dim3(256), 0, s, img, B, H, W, center, scale,
-                crop, out);
+                crop, out, boxes_per_image);
 }
 void track_box_launch(const double* kp_image, const float* sm, int cs, int B, int H, int W, int crop, float margin, float min_score,
                       int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0, hipStream_t s) {

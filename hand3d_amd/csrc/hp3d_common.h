@@ -394,8 +394,9 @@ void avgpool8_launch(const float* x, int B, int H, int W, int C, float* out, int
 void resize_bilinear_launch(const float* x, int B, int H, int W, int C, int in_cs,
                             int oh, int ow, float* out, hipStream_t s);
 void preprocess_u8_launch(const unsigned char* img, int B, int H, int W, int oh, int ow, float* out, hipStream_t s);
+// box b crops image b / boxes_per_image: B boxes, B / boxes_per_image images
 void crop_and_resize_launch(const float* img, int B, int H, int W, int C, const float* center,
-                            const float* scale, int crop, float* out, hipStream_t s);
+                            const float* scale, int crop, float* out, hipStream_t s, int boxes_per_image = 1);
 
 struct MaskBuffers {           // per-call scratch owned by the executor
     unsigned long long* argmax_key;  // [B]
@@ -433,7 +434,7 @@ void kp_detect_launch(const float* sm, int B, int h, int w, int C, int cs, int o
 // the next crop box from the keypoints kp_detect wrote (+ confidence from the 32 x 32 score maps `sm`, channel stride cs, may be null;
 // detected0, may be null, is zeroed); a detect step's per-image choice between HandSegNet's box and the tracked one
 void crop_and_resize_u8_launch(const unsigned char* img, int B, int H, int W, const float* center, const float* scale, int crop,
-                               float* out, hipStream_t s);
+                               float* out, hipStream_t s, int boxes_per_image = 1);
 void track_box_launch(const double* kp_image, const float* sm, int cs, int B, int H, int W, int crop, float margin, float min_score,
                       int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0, hipStream_t s);
 void track_select_launch(const int* lost_prev, const float* det_center, const float* det_scale, int B, int force_all,
@@ -446,6 +447,9 @@ size_t mask_grow_global_words(int H, int W);     // per-image scratch of mask_gr
 // the same growth with the bitmaps in global scratch (B x mask_grow_global_words words): any frame size
 void mask_grow_global_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltmax, unsigned* scratch, float* mask_out,
                              float* center, float* crop_size, float* scale, int* seed, hipStream_t s);
+// up to K hands per image: outputs [B,K,...]; needs mb.fg; scratch null = bitmaps in LDS, else as mask_grow_global_launch
+void mask_grow_multi_launch(const MaskBuffers& mb, int B, int H, int W, int K, int min_area, int empty_fltmax, unsigned* scratch,
+                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

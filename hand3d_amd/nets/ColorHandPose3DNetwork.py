@@ -135,6 +135,21 @@ class ColorHandPose3DNetwork(object):
         o = self.engine.infer_full(image, hand_side, outputs=('coord3d', 'kp_crop', 'kp_hw', 'scale', 'center'))
         return o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center']
 
+    def inference_hands(self, image, hand_side, max_hands, evaluation=True):
+        """ Not in the reference class: inference() for up to `max_hands` (1 ... 4) hands per frame from ONE HandSegNet pass
+            (DESIGN.md 4.12).  Hand k of a frame is the k-th object of the detection map in descending peak foreground score;
+            hand 0 is inference()'s hand.  `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3]; `hand_side` [B,K,2], one
+            row per slot.  Returns inference()'s tuple with a K axis -- hand_scoremap [B,H,W,2], image_crop [B,K,256,256,3],
+            scale_crop [B,K], center [B,K,2], keypoints_scoremap [B,K,256,256,21], keypoint_coord3d [B,K,21,3] -- plus
+            valid [B,K] (0: the slot holds no hand; its outputs come from the fall-back crop), area [B,K] (pixels of the hand's
+            mask) and keypoint_hw [B,K,21,2] float64 (row, col in the input image). """
+        self._check_eval(evaluation)
+        if np.asarray(image).dtype == np.uint8:
+            o = self.engine.infer_hands_u8(image, hand_side, max_hands, H=np.shape(image)[1], W=np.shape(image)[2])
+        else:
+            o = self.engine.infer_hands(image, hand_side, max_hands)
+        return (o['scoremap'], o['crop'], o['scale'], o['center'], o['kpmap'], o['coord3d'], o['valid'], o['area'], o['kp_hw'])
+
     def track(self, image, hand_side):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with

@@ -152,6 +152,9 @@ int hp3d_sync(hp3d_ctx* ctx);
  *          "track_min_score" = "off" (default) | a number: a tracked image counts as lost when its confidence is below it.  A useful
  *                            value depends on the trained weights: callers calibrate it on the confidence the steps return;
  *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image;
+ *          "hands_min_area" = "0" (default: off) | N: hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer than N pixels
+ *                            instead of reporting them as hands.  A useful value depends on the trained weights: callers calibrate it on
+ *                            the `area` every call returns;
  *          "f16_impl"     = "h16" (default) | "mfma" | "h16_force": with half-precision trunks (hp3d_finalize_weights dtype 1),
  *                            the 3x3 / stride-1 layers with Cin >= 64 run on the half-precision trunk kernel (conv_h16.hip)
  *                            whenever their grid fills the chip | never (general kernel only) | whenever the shape allows
@@ -322,6 +325,39 @@ int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw
 int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, const float* center,
                             const float* scale, int crop_size, float* out);
 
+/* ---- several hands per frame --------------------------------------------------
+ * The whole-path calls above keep ONE object of HandSegNet's detection map per image: the one that grows from the arg-max of the
+ * foreground score (single_obj_scoremap, utils/general.py:233-268).  These calls return up to K of them, 1 <= K <= HP3D_MAX_HANDS, from
+ * one HandSegNet pass.  With R = the detection map: the next object grows (21x21 dilation inside R, the reference's pass cap) from the
+ * first arg-max of the foreground score over R and is then removed from R, so objects are pairwise disjoint; an object of at least
+ * option "hands_min_area" pixels becomes the next hand; at most 4 K objects are grown per image.  Hands come in the order of discovery
+ * (descending peak score, ties to the first pixel in row-major order).  Slot 0 with "hands_min_area" off is hp3d_infer_full's hand bit for
+ * bit; where the detection map is empty it keeps that call's fall-back box and reports valid = 0.  Slots left over: valid = 0, area = 0,
+ * zero mask, the fall-back box of option "empty_reduce".  Per hand, centre / crop size / scale as hp3d_infer_full computes them.  An object
+ * the pass cap cuts short leaves its remainder in R, which can come back as a later hand.
+ * All B * K slots run through PoseNet2D and the lifting stage, absent ones on their fall-back crop (no compaction: one kernel plan per
+ * call, no host wait); slot j of image b is index b * K + j of every per-hand output.
+ * hp3d_infer_hands      image [B,H,W,3], hand_side [B,K,2] (per slot: which hand is left or right is the caller's knowledge) ->
+ *                       hand_scoremap [B,H,W,2], image_crop [B,K,256,256,3], scale_crop [B,K], center [B,K,2],
+ *                       keypoints_scoremap [B,K,256,256,21], keypoint_coord3d [B,K,21,3], hand_mask [B,K,H,W],
+ *                       keypoint_hw_crop [B,K,21,2] int32, keypoint_hw [B,K,21,2] float64 (as hp3d_infer_full_kp),
+ *                       valid [B,K] int32, area [B,K] int32 (pixels of the hand's mask).  Any output may be NULL.
+ * hp3d_infer_hands_dev  the same on device pointers, stream-ordered.
+ * hp3d_infer_hands_u8   uint8 frames [B,Hin,Win,3] on the host, normalised and resized to H x W on the device as hp3d_infer_full_kp_u8.
+ * Batches run in chunks of at most micro_batch / K frames on one stream; half-precision trunks work; no graph replay, no second stream.
+ * K outside 1 ... HP3D_MAX_HANDS or a NULL hand_side -> HP3D_ERR_ARG before any launch.                                          */
+#define HP3D_MAX_HANDS 4
+int hp3d_infer_hands(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* hand_scoremap,
+                     float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                     float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area);
+int hp3d_infer_hands_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* hand_scoremap,
+                         float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                         float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area);
+int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
+                        float* hand_scoremap, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                        float* keypoint_coord3d, float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid,
+                        int32_t* area);
+
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65
  *                      x [B,H,W,Cin], w HWIO, SAME padding incl. the asymmetric stride-2 case.
@@ -341,6 +377,9 @@ int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H
  *                      3 * H * (ceil(W / 32) + 1) + 2 words <= 159 KB), in global scratch beyond; larger maps -> HP3D_ERR_ARG
  *                      "map too large".  With "mask_grow" = "lds" maps beyond the LDS size are refused.
  *                      -> mask [B,H,W], center [B,2], crop_size [B,1] (before *1.25), scale [B,1], seed int32 [B,2]
+ * hp3d_masks_from_scoremap the mask stage of hp3d_infer_hands: scoremap [B,H,W,2], K -> mask [B,K,H,W], center [B,K,2],
+ *                      crop_size [B,K], scale [B,K], seed int32 [B,K,2] ((-1, -1) for an absent slot), valid [B,K], area [B,K] int32;
+ *                      same size limits and "mask_grow" forms as hp3d_mask_from_scoremap
  * hp3d_fc              NetworkOps.fully_connected(_relu)                      utils/general.py:112-136
  * hp3d_argmax2d        detect_keypoints (per-channel first arg-max)           utils/general.py:331-344
  *                      x [B,H,W,C] -> int32 [B,C,2] (row, col)                                    */
@@ -355,6 +394,8 @@ int hp3d_crop_and_resize(hp3d_ctx* ctx, const float* image, int B, int H, int W,
                          const float* center, const float* scale, int crop_size, float* out);
 int hp3d_mask_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W,
                             float* mask, float* center, float* crop_size, float* scale, int32_t* seed);
+int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, float* mask, float* center,
+                             float* crop_size, float* scale, int32_t* seed, int32_t* valid, int32_t* area);
 int hp3d_fc(hp3d_ctx* ctx, const float* x, int B, int Cin, const float* w, const float* bias,
             int Cout, int act, float* out);
 int hp3d_argmax2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C, int32_t* out_rc);
