@@ -6,6 +6,7 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py frames_dir/                  (*.png / *.jpg in name order; needs ./weights/*.pickle, like run.py)
     python examples/track.py frames.npy                   (uint8 or float [N,H,W,3])
     python examples/track.py --synthetic                  (seeded synthetic weights + frames)
+    python examples/track.py --synthetic --hands 2        (up to K hands per frame, each in its own slot: DESIGN.md 4.13)
 """
 import glob
 import json
@@ -20,6 +21,8 @@ if __name__ == '__main__':
     ap = parser(__doc__)
     ap.add_argument('frames', nargs='?')
     ap.add_argument('--redetect', type=int, default=0, help='every N-th frame detects anew (0: only when the hand is lost)')
+    ap.add_argument('--hands', type=int, default=0, metavar='K',
+                    help='follow up to K hands per frame, each in its own slot (0: the single-hand tracker)')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -50,6 +53,9 @@ if __name__ == '__main__':
     net.engine.set_option('track_min_score', a.min_score)
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
     net.track_reset()
+    net.track_hands_reset()
+    if a.hands:
+        hand_side_v = np.tile(hand_side_v, (1, a.hands, 1)).reshape(1, a.hands, 2)          # which slot holds a left hand is the caller's knowledge
     for i, frame in enumerate(frames):
         frame = np.asarray(frame)
         if frame.dtype == np.uint8:
@@ -58,6 +64,16 @@ if __name__ == '__main__':
             image_v = frame[None].astype(np.float32) / 255.0 - 0.5
         else:
             image_v = frame[None].astype(np.float32)
+        ndet = net.engine.counter('track_hands_detect_steps')
+        if a.hands:
+            coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands)
+            print(json.dumps({'frame': i, 'step': 'detect' if net.engine.counter('track_hands_detect_steps') > ndet else 'tracked',
+                              'slots': [{'slot': k, 'valid': int(valid[0, k]), 'detected': int(detected[0, k]), 'area': int(area[0, k]),
+                                         'center': center[0, k].tolist(), 'scale': float(scale[0, k]),
+                                         'confidence': float(confidence[0, k]), 'lost': int(lost[0, k]),
+                                         'wrist_hw': kp_hw[0, k, 0].tolist(), 'wrist_xyz': coord3d[0, k, 0].tolist()}
+                                        for k in range(a.hands)]}))
+            continue
         coord3d, kp_hw, kp_hw_crop, scale, center, confidence, lost, detected = net.track(image_v, hand_side_v)
         print(json.dumps({'frame': i, 'step': 'detect' if detected[0] else 'tracked', 'center': center[0].tolist(),
                           'scale': float(scale[0, 0]), 'confidence': float(confidence[0]), 'lost': int(lost[0]),

@@ -63,6 +63,13 @@ _SIGNATURES = {
     'hp3d_infer_hands_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13),
     'hp3d_infer_hands_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
     'hp3d_masks_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    'hp3d_masks_from_scoremap_keep': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    'hp3d_track_hands_reset': (C.c_int, [_ctx]),
+    'hp3d_track_hands_seed': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hp3d_track_hands_step': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15),
+    'hp3d_track_hands_step_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15),
+    'hp3d_track_hands_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_track_hands_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 7),
     'hp3d_track_reset': (C.c_int, [_ctx]),
     'hp3d_track_seed': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'hp3d_track_step': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
@@ -375,9 +382,11 @@ class Engine(object):
         self._chk(self.lib.hp3d_infer_hands_dev(self.h, B, H, W, K, v(image_ptr), v(hand_side_ptr), v(scoremap), v(crop), v(scale),
                                                 v(center), v(kpmap), v(coord3d), v(mask), v(kp_crop), v(kp_hw), v(valid), v(area)))
 
-    def masks_from_scoremap(self, scoremap, max_hands):
+    def masks_from_scoremap(self, scoremap, max_hands, keep=None):
         """The mask stage of infer_hands alone: scoremap [B,H,W,2] -> dict of mask [B,K,H,W], center [B,K,2], crop_size [B,K],
-        scale [B,K], seed int32 [B,K,2], valid [B,K], area [B,K]."""
+        scale [B,K], seed int32 [B,K,2], valid [B,K], area [B,K].  keep = (keep [B,K], center [B,K,2], scale [B,K]): the mask stage of a
+        multi-hand tracker's detect step -- objects a kept slot claims are dropped and counted in the extra output
+        claimed [B,K], the others fill the free slots, kept slots come back as absent ones."""
         sm = _f32(scoremap)
         B, H, W, c2 = sm.shape
         assert c2 == 2
@@ -385,9 +394,98 @@ class Engine(object):
         o = {'mask': np.empty((B, K, H, W), np.float32), 'center': np.empty((B, K, 2), np.float32),
              'crop_size': np.empty((B, K), np.float32), 'scale': np.empty((B, K), np.float32),
              'seed': np.empty((B, K, 2), np.int32), 'valid': np.empty((B, K), np.int32), 'area': np.empty((B, K), np.int32)}
-        self._chk(self.lib.hp3d_masks_from_scoremap(self.h, _ptr(sm), B, H, W, K,
-                                                    *[_ptr(o[k]) for k in ('mask', 'center', 'crop_size', 'scale', 'seed', 'valid', 'area')]))
+        outs = [_ptr(o[k]) for k in ('mask', 'center', 'crop_size', 'scale', 'seed', 'valid', 'area')]
+        if keep is None:
+            self._chk(self.lib.hp3d_masks_from_scoremap(self.h, _ptr(sm), B, H, W, K, *outs))
+            return o
+        kk = np.ascontiguousarray(keep[0], dtype=np.int32)
+        kc, ks = _f32(keep[1]), _f32(keep[2])
+        assert kk.shape == (B, K) and kc.shape == (B, K, 2) and ks.shape == (B, K), "keep must be ([B,K], [B,K,2], [B,K])"
+        o['claimed'] = np.empty((B, K), np.int32)
+        self._chk(self.lib.hp3d_masks_from_scoremap_keep(self.h, _ptr(sm), B, H, W, K, _ptr(kk), _ptr(kc), _ptr(ks), *outs, _ptr(o['claimed'])))
         return o
+
+    # -- tracking several hands per frame (include/hp3d.h) ------------------------------
+    _TRACK_HANDS_ORDER = ('crop', 'scale', 'center', 'kpmap', 'coord3d', 'kp_crop', 'kp_hw', 'confidence', 'lost', 'detected', 'valid',
+                          'area', 'claimed')
+
+    @staticmethod
+    def _track_hands_outputs(B, K, want_kpmap):
+        i32 = lambda: np.empty((B, K), np.int32)
+        return {'crop': np.empty((B, K, 256, 256, 3), np.float32), 'scale': np.empty((B, K), np.float32),
+                'center': np.empty((B, K, 2), np.float32),
+                'kpmap': np.empty((B, K, 256, 256, 21), np.float32) if want_kpmap else None,
+                'coord3d': np.empty((B, K, 21, 3), np.float32), 'kp_crop': np.empty((B, K, 21, 2), np.int32),
+                'kp_hw': np.empty((B, K, 21, 2), np.float64), 'confidence': np.empty((B, K), np.float32),
+                'lost': i32(), 'detected': i32(), 'valid': i32(), 'area': i32(), 'claimed': i32()}
+
+    def track_hands_reset(self):
+        """The next track_hands_step detects and keeps no slot."""
+        self._chk(self.lib.hp3d_track_hands_reset(self.h))
+
+    def track_hands_seed(self, center, scale, valid, H, W):
+        """Start from boxes the caller has: center [B,K,2] (row, col), scale [B,K], valid [B,K] (at least one valid slot per image);
+        the next step at (B, K, H, W) is a tracked one."""
+        center, scale = _f32(center), _f32(scale)
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        assert scale.ndim == 2, "scale must be [B,K]"
+        B, K = scale.shape
+        assert center.shape == (B, K, 2) and valid.shape == (B, K), "center must be [B,K,2], valid [B,K]"
+        self._chk(self.lib.hp3d_track_hands_seed(self.h, B, int(H), int(W), K, _ptr(center), _ptr(scale), _ptr(valid)))
+
+    def track_hands_step(self, image, hand_side, max_hands, want_kpmap=False):
+        """One video step with max_hands slots per frame on float32 frames [B,H,W,3], hand_side [B,K,2].  Returns a dict of [B,K,...]
+        arrays: track_step's outputs per slot plus valid, area (pixel count where detected = 1) and claimed (objects the slot claimed
+        on a detect step).  The slot index is the hand's identity for as long as the slot is not lost."""
+        image, hand_side = _f32(image), _f32(hand_side)
+        assert image.ndim == 4 and image.shape[3] == 3, "image must be [B,H,W,3]"
+        B, H, W, _ = image.shape
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._track_hands_outputs(B, K, want_kpmap)
+        self._chk(self.lib.hp3d_track_hands_step(self.h, B, H, W, K, _ptr(image), _ptr(hand_side),
+                                                 *[_ptr(o[k]) for k in self._TRACK_HANDS_ORDER]))
+        return o
+
+    def track_hands_step_u8(self, image_u8, hand_side, max_hands, H=None, W=None, want_kpmap=False):
+        """track_hands_step on uint8 frames [B,Hin,Win,3]; tracked steps crop straight from them.  (H, W) default to the frame size,
+        the only size the engine accepts here."""
+        img = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        hand_side = _f32(hand_side)
+        assert img.ndim == 4 and img.shape[3] == 3, "image must be [B,Hin,Win,3] uint8"
+        B, Hin, Win, _ = img.shape
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._track_hands_outputs(B, K, want_kpmap)
+        self._chk(self.lib.hp3d_track_hands_step_u8(self.h, B, Hin, Win, _ptr(img), int(H or Hin), int(W or Win), K, _ptr(hand_side),
+                                                    *[_ptr(o[k]) for k in self._TRACK_HANDS_ORDER]))
+        return o
+
+    def track_hands_step_dev(self, B, H, W, K, image_ptr, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0, coord3d=0, kp_crop=0,
+                             kp_hw=0, confidence=0, lost=0, detected=0, valid=0, area=0, claimed=0):
+        """Device-pointer variant (ints); stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_hands_step_dev(self.h, B, H, W, K, v(image_ptr), v(hand_side_ptr), v(crop), v(scale), v(center),
+                                                     v(kpmap), v(coord3d), v(kp_crop), v(kp_hw), v(confidence), v(lost), v(detected),
+                                                     v(valid), v(area), v(claimed)))
+
+    def track_hands_box(self, keypoint_hw, valid, box_center, box_scale, H, W, score32=None, margin=None):
+        """track_box per slot with valid gating: keypoint_hw [B,K,21,2], valid [B,K], the boxes the slots cropped with ([B,K,2], [B,K])
+        -> (center [B,K,2], scale [B,K], confidence [B,K], lost [B,K]); an absent slot holds its box with lost = 0."""
+        kp = np.ascontiguousarray(keypoint_hw, dtype=np.float64)
+        assert kp.ndim == 4 and kp.shape[2:] == (21, 2), "keypoint_hw must be [B,K,21,2]"
+        B, K = kp.shape[:2]
+        sm = None if score32 is None else _f32(score32)
+        assert sm is None or sm.shape == (B, K, 32, 32, 21), "score32 must be [B,K,32,32,21]"
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        bc, bs = _f32(box_center), _f32(box_scale)
+        assert valid.shape == (B, K) and bc.shape == (B, K, 2) and bs.shape == (B, K)
+        center, scale = np.empty((B, K, 2), np.float32), np.empty((B, K), np.float32)
+        conf, lost = np.empty((B, K), np.float32), np.empty((B, K), np.int32)
+        assert margin is None or margin > 0, "margin must be positive"
+        self._chk(self.lib.hp3d_track_hands_box(self.h, B, K, int(H), int(W), _ptr(kp), _ptr(sm), 0.0 if margin is None else float(margin),
+                                                _ptr(valid), _ptr(bc), _ptr(bs), _ptr(center), _ptr(scale), _ptr(conf), _ptr(lost)))
+        return center, scale, conf, lost
 
     # -- tracking: a hand across video frames (include/hp3d.h, DESIGN.md 4.11) -------------------------
     def track_reset(self):

@@ -307,6 +307,7 @@ struct Counters {
     long mask_grow_multi_launches = 0;              // mask growths of the multi-hand kernels (either form)
     long track_detect_steps = 0, track_tracked_steps = 0;      // hp3d_track_step*: steps that ran HandSegNet / that did not
     long crop_u8_launches = 0;                      // crops taken straight from a uint8 frame (crop_and_resize_u8_kernel)
+    long track_hands_detect_steps = 0, track_hands_tracked_steps = 0;      // hp3d_track_hands_step*: as track_*_steps
 };
 
 // What a context knows about the hands it follows (hp3d_track_*): the boxes for the next step, on the device, and the host's copy of the
@@ -325,6 +326,26 @@ struct TrackState {
     bool valid = false;                 // box[cur] holds boxes for (B, H, W)
     int B = 0, H = 0, W = 0;
     int since = 0;                      // tracked steps since the last detect step
+};
+
+// The multi-hand tracker's state (hp3d_track_hands_*): the same per slot (b, j) at index b * K + j, separate from
+// TrackState.  flags = valid [n] | lost [n] (n = B * K slots of the current shape), so that one 8 n-byte copy carries both to the host.
+struct TrackHandsState {
+    int cap = 0;                        // slots the buffers hold
+    float* center[2] = {nullptr, nullptr};
+    float* scale[2] = {nullptr, nullptr};
+    float* conf = nullptr;
+    int *flags = nullptr, *detected = nullptr, *area = nullptr, *claimed = nullptr;
+    int* keep = nullptr;                // valid and not lost after the last step: what a detect step behind it keeps
+    int* h_flags = nullptr;             // page-locked: the last step's valid | lost (copied behind the step, ev_flags)
+    hipEvent_t ev_flags = nullptr;
+    bool pending = false;
+    int cur = 0;
+    bool ok = false;                    // box[cur] and the flags hold a state for (B, K, H, W)
+    int B = 0, K = 0, H = 0, W = 0;
+    int since = 0;                      // tracked steps since the last detect step
+    int* valid() const { return flags; }
+    int* lost() const { return flags + (size_t)B * K; }
 };
 
 }  // namespace
@@ -389,6 +410,7 @@ struct hp3d_ctx : Options, Counters {
     unsigned* d_mgscratch = nullptr;                // the global-scratch kernel's bitmaps, B x mask_grow_global_words(H, W) words
     size_t mg_words = 0;
     TrackState track;
+    TrackHandsState track_hands;
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -1384,8 +1406,9 @@ int copy_out(hp3d_ctx* ctx, float* dst, const float* src, size_t n, bool dev) {
 // stages 2-8 of the full path on device-resident image/hand_side
 // K > 0: the multi-hand form -- HandSegNet once, the soft-max also writes fg, up to K hands per image into slots
 // b * K + j of d_center / d_scale / d_cropsize / d_seed / d_valid / d_area (/ d_mask), and B * K crops from the B frames
+// mk (K > 0): the slots a multi-hand tracking step keeps; that step crops itself (do_crop = false)
 int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W, int want_mask, bool image_hot = false, bool do_crop = true,
-                        int K = 0) {
+                        int K = 0, const MaskKeep& mk = MaskKeep()) {
     CHK(run_handsegnet(ctx, d_image, B, H, W, image_hot));
     MaskBuffers mb{ctx->d_keys, ctx->d_det, K > 0 ? ctx->d_fg : nullptr};
     {
@@ -1398,10 +1421,11 @@ int run_detect_and_crop(hp3d_ctx* ctx, const float* d_image, int B, int H, int W
             const bool global = mask_grow_global(ctx, H, W);
             mask_grow_multi_launch(mb, B, H, W, K, ctx->hands_min_area, ctx->empty_fltmax, global ? ctx->d_mgscratch : nullptr,
                                    want_mask ? ctx->d_mask : nullptr, ctx->d_center, ctx->d_cropsize, ctx->d_scale, ctx->d_seed, ctx->d_valid,
-                                   ctx->d_area, ctx->stream);
+                                   ctx->d_area, ctx->stream, mk);
             ++ctx->mask_grow_multi_launches;
             if (global) ++ctx->mask_grow_global_launches;
         }
+        if (!do_crop) { HIPCHK(ctx, hipGetLastError()); return 0; }
         ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * B * (H * W * 3 + K * 256 * 256 * 3));
         crop_and_resize_launch(d_image, B * K, H, W, 3, ctx->d_center, ctx->d_scale, 256, ctx->d_crop, ctx->stream, K);
         HIPCHK(ctx, hipGetLastError());
@@ -1738,6 +1762,8 @@ void track_free(hp3d_ctx* ctx) {
 // from the previous step's `lost` flags (4 * B bytes that travel behind that step); the whole batch detects when any image is lost:
 // one kernel plan per step, no gather of the lost images.  image_u8 (host, frame = network size) instead of image: the tracked
 // step crops straight from the uint8 frame, the detect step normalises it first (preprocess_u8) as hp3d_infer_full_u8 does.
+// (track_hands_step_impl below repeats this function's frame per slot: a fix to the upload, the chunk loop, the kp_up / kp_work pair or
+//  the copy_out sequence here belongs there as well.)
 int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, const unsigned char* image_u8, const float* hand_side,
                     float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
                     double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev) {
@@ -1919,6 +1945,191 @@ int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
     return 0;
 }
 
+// ---- tracking several hands per frame --------------------------------------------------------------------
+int ensure_track_hands(hp3d_ctx* ctx, int n) {
+    TrackHandsState& T = ctx->track_hands;
+    if (n <= T.cap) return 0;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }
+    for (int i = 0; i < 2; ++i) {
+        CHK(dev_realloc(ctx, &T.center[i], (size_t)n * 2));
+        CHK(dev_realloc(ctx, &T.scale[i], (size_t)n));
+    }
+    CHK(dev_realloc(ctx, &T.conf, (size_t)n));
+    CHK(dev_realloc(ctx, &T.flags, (size_t)n * 2));
+    CHK(dev_realloc(ctx, &T.detected, (size_t)n));
+    CHK(dev_realloc(ctx, &T.area, (size_t)n));
+    CHK(dev_realloc(ctx, &T.claimed, (size_t)n));
+    CHK(dev_realloc(ctx, &T.keep, (size_t)n));
+#ifdef HP3D_EMU
+    free(T.h_flags);
+    T.h_flags = (int*)malloc(sizeof(int) * (size_t)n * 2);
+    if (!T.ev_flags) HIPCHK(ctx, hipEventCreate(&T.ev_flags));
+#else
+    if (T.h_flags) HIPCHK(ctx, hipHostFree(T.h_flags));
+    T.h_flags = nullptr;
+    HIPCHK(ctx, hipHostMalloc((void**)&T.h_flags, sizeof(int) * (size_t)n * 2, hipHostMallocDefault));
+    if (!T.ev_flags) HIPCHK(ctx, hipEventCreateWithFlags(&T.ev_flags, hipEventDisableTiming));
+#endif
+    if (!T.h_flags) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "multi-hand tracking state: host allocation failed");
+    T.cap = n;
+    T.ok = false;
+    return 0;
+}
+
+void track_hands_free(hp3d_ctx* ctx) {
+    TrackHandsState& T = ctx->track_hands;
+    for (int i = 0; i < 2; ++i) {
+        if (T.center[i]) hipFree(T.center[i]);
+        if (T.scale[i]) hipFree(T.scale[i]);
+    }
+    for (void* p : {(void*)T.conf, (void*)T.flags, (void*)T.detected, (void*)T.area, (void*)T.claimed, (void*)T.keep})
+        if (p) hipFree(p);
+#ifdef HP3D_EMU
+    free(T.h_flags);
+#else
+    if (T.h_flags) hipHostFree(T.h_flags);
+#endif
+    if (T.ev_flags) hipEventDestroy(T.ev_flags);
+    T = TrackHandsState();
+}
+
+// One video step with K slots per frame.  A slot follows its hand for as long as it is not lost: the slot index is the hand's identity.
+// DETECT step: HandSegNet once, the soft-max with fg, one claimed multi-hand growth per chunk (slots that are valid and not lost are
+// kept: an object one of them claims is dropped, the others fill the free slots in the order of discovery), the per-slot select, then
+// the crop.  TRACKED step: the K crops of a frame come from the state's boxes.  Behind the crop both are infer_hands_impl's back half
+// at batch nb * K plus the per-slot box rule.  Decided on the host, before anything is enqueued, from the valid | lost flags that travel
+// behind the previous step; the whole batch detects together; absent slots run on their fall-back crop (no compaction).
+// (The frame of this function -- uint8 upload, profile save / restore, chunk loop, kp_up / kp_work, copy_out sequence -- repeats
+//  track_step_impl's, which this change leaves as it is: a fix to one of the two belongs in the other as well.)
+int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, const float* hand_side,
+                          float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
+                          double* kp_image, float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area,
+                          int32_t* claimed, bool dev) {
+    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    CHK(check_img(ctx, B, H, W));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TrackHandsState& T = ctx->track_hands;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
+    const int n = B * K;
+    const bool fresh = !T.ok || T.B != B || T.K != K || T.H != H || T.W != W;
+    bool any_lost = false, no_hand = false;      // a valid slot was lost / an image has nothing to follow
+    if (!fresh)
+        for (int b = 0; b < B; ++b) {
+            bool any_valid = false;
+            for (int j = 0; j < K; ++j) {
+                const bool v = T.h_flags[b * K + j] != 0;
+                any_valid = any_valid || v;
+                any_lost = any_lost || (v && T.h_flags[n + b * K + j] != 0);
+            }
+            no_hand = no_hand || !any_valid;
+        }
+    const bool sched = ctx->track_redetect > 0 && T.since + 1 >= ctx->track_redetect;
+    const bool detect = fresh || any_lost || no_hand || sched;
+    CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
+    const int front = auto_micro_batch(ctx, B, H, W), back = auto_micro_batch(ctx, n, 256, 256);
+    int mb = front <= 0 ? B : std::min(front, B);
+    if (back > 0) mb = std::min(mb, std::max(1, back / K));
+    CHK(ensure_arena(ctx, mb, H, W, mb * K));
+    CHK(ensure_track_hands(ctx, n));
+    T.ok = false;                                        // a step that fails half way leaves no state behind
+    T.B = B; T.K = K; T.H = H; T.W = W;                  // (the flags' layout: lost() = flags + B K)
+    if (fresh) HIPCHK(ctx, hipMemsetAsync(T.keep, 0, sizeof(int) * (size_t)n, ctx->stream));      // nothing to keep
+    if (image_u8) {
+        const size_t nbytes = (size_t)B * H * W * 3;
+        if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int saved_prof = ctx->profiling;
+    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
+    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    const int cur = T.cur, nxt = T.cur ^ 1;
+    for (int b0 = 0; b0 < B; b0 += mb) {
+        const int nb = std::min(mb, B - b0), ns = nb * K;
+        const size_t s0 = (size_t)b0 * K;
+        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one step = one profile: keep the earlier chunks
+        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
+        const float* d_hs = hand_side + s0 * 2;
+        const unsigned char* d_u8 = image_u8 ? ctx->d_u8 + (size_t)b0 * H * W * 3 : nullptr;
+        if (!dev) {
+            CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false));
+            d_hs = ctx->d_hs;
+            if (!image_u8) { CHK(copy_in(ctx, ctx->d_image, d_img, (size_t)nb * H * W * 3, false)); d_img = ctx->d_image; }
+        }
+        float* bc = T.center[cur] + s0 * 2;
+        float* bs = T.scale[cur] + s0;
+        if (detect) {
+            if (image_u8) {
+                ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
+                preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
+                HIPCHK(ctx, hipGetLastError());
+                d_img = ctx->d_image;
+            }
+            MaskKeep mk;
+            mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, image_u8 != nullptr, false, K, mk));
+            {
+                ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
+                track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
+                                          T.detected + s0, T.area + s0, ctx->stream);
+            }
+            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
+            crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+        } else if (image_u8) {
+            ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
+            crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+            ++ctx->crop_u8_launches;
+        } else {
+            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
+            crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
+        float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
+        int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
+        double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
+        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
+            if (kpmap_out) {
+                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
+                resize_bilinear_launch(ctx->d_sm[2], ns, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
+            }
+            return 0;
+        };
+        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
+            CHK(run_kp_detect(ctx, ns, kpc_out, kpi_out, dev, bs, bc));
+            ProfScope ps(ctx, "track_hands_box", "track_hands_box", 0.0, 4.0 * ns * 32 * 32 * 21);
+            int* zero = detect ? nullptr : T.detected + s0;
+            track_hands_box_launch(dev && kpi_out ? kpi_out : ctx->d_kpimg, ctx->d_sm[2], 32, ns, H, W, 256, ctx->track_margin,
+                                   ctx->track_min_score, ctx->track_use_min_score, T.valid() + s0, bc, bs, T.center[nxt] + s0 * 2,
+                                   T.scale[nxt] + s0, T.conf + s0, T.lost() + s0, T.keep + s0, zero, detect ? nullptr : T.area + s0,
+                                   detect ? nullptr : T.claimed + s0, ctx->stream);
+            return 0;
+        };
+        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        auto offi = [&](int32_t* p) { return (float*)(p ? p + s0 : nullptr); };           // (int32: four bytes each, as copy_out counts)
+        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
+        CHK(copy_out(ctx, off(scale_crop, 1), bs, (size_t)ns, dev));
+        CHK(copy_out(ctx, off(center, 2), bc, (size_t)ns * 2, dev));
+        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
+        CHK(copy_out(ctx, off(confidence, 1), T.conf + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, offi(lost), (const float*)(T.lost() + s0), (size_t)ns, dev));
+        CHK(copy_out(ctx, offi(detected), (const float*)(T.detected + s0), (size_t)ns, dev));
+        CHK(copy_out(ctx, offi(valid), (const float*)(T.valid() + s0), (size_t)ns, dev));
+        CHK(copy_out(ctx, offi(area), (const float*)(T.area + s0), (size_t)ns, dev));
+        CHK(copy_out(ctx, offi(claimed), (const float*)(T.claimed + s0), (size_t)ns, dev));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(T.h_flags, T.flags, sizeof(int) * (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(T.ev_flags, ctx->stream));
+    T.pending = true;
+    T.cur = nxt; T.ok = true;
+    T.since = detect ? 0 : T.since + 1;
+    ++(detect ? ctx->track_hands_detect_steps : ctx->track_hands_tracked_steps);
+    if (!dev) return finish_op(ctx);
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -2072,6 +2283,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
     if (ctx->d_det) hipFree(ctx->d_det);
     if (ctx->d_mgscratch) hipFree(ctx->d_mgscratch);
     track_free(ctx);
+    track_hands_free(ctx);
     if (ctx->d_u8) hipFree(ctx->d_u8);
     if (ctx->blob16) hipFree(ctx->blob16);
     if (ctx->d_concat16) hipFree(ctx->d_concat16);
@@ -2521,8 +2733,9 @@ int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* i
                             keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, false);
 }
 
-int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, float* mask, float* center,
-                             float* crop_size, float* scale, int32_t* seed, int32_t* valid, int32_t* area) {
+static int masks_from_scoremap_impl(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, const int32_t* keep,
+                                    const float* keep_center, const float* keep_scale, float* mask, float* center, float* crop_size,
+                                    float* scale, int32_t* seed, int32_t* valid, int32_t* area, int32_t* claimed) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!scoremap || B < 1 || H < 1 || W < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
@@ -2548,9 +2761,18 @@ int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H,
     int* d_area = S.alloc<int>(ns); NN(ctx, d_area);
     unsigned* d_scr = nullptr;
     if (global) { d_scr = S.alloc<unsigned>((size_t)B * mask_grow_global_words(H, W)); NN(ctx, d_scr); }
+    MaskKeep mk;
+    int* d_claimed = nullptr;
+    if (keep) {
+        mk.keep = S.upload((const int*)keep, ns); NN(ctx, mk.keep);
+        mk.center = S.upload(keep_center, ns * 2); NN(ctx, mk.center);
+        mk.scale = S.upload(keep_scale, ns); NN(ctx, mk.scale);
+        d_claimed = S.alloc<int>(ns); NN(ctx, d_claimed);
+        mk.claimed = d_claimed;
+    }
     seg_softmax_launch(d_sm, B, H, W, mb, ctx->stream);
     mask_grow_multi_launch(mb, B, H, W, K, ctx->hands_min_area, ctx->empty_fltmax, d_scr, d_mask, d_c, d_cs, d_sc, d_seed, d_valid, d_area,
-                           ctx->stream);
+                           ctx->stream, mk);
     ++ctx->mask_grow_multi_launches;
     if (global) ++ctx->mask_grow_global_launches;
     if (mask) HIPCHK(ctx, hipMemcpyAsync(mask, d_mask, ns * H * W * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -2560,6 +2782,129 @@ int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H,
     if (seed) HIPCHK(ctx, hipMemcpyAsync(seed, d_seed, sizeof(int) * ns * 2, hipMemcpyDeviceToHost, ctx->stream));
     if (valid) HIPCHK(ctx, hipMemcpyAsync(valid, d_valid, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
     if (area) HIPCHK(ctx, hipMemcpyAsync(area, d_area, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (claimed && d_claimed) HIPCHK(ctx, hipMemcpyAsync(claimed, d_claimed, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, float* mask, float* center,
+                             float* crop_size, float* scale, int32_t* seed, int32_t* valid, int32_t* area) {
+    return masks_from_scoremap_impl(ctx, scoremap, B, H, W, K, nullptr, nullptr, nullptr, mask, center, crop_size, scale, seed, valid, area,
+                                    nullptr);
+}
+
+int hp3d_masks_from_scoremap_keep(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, const int32_t* keep,
+                                  const float* keep_center, const float* keep_scale, float* mask, float* center, float* crop_size,
+                                  float* scale, int32_t* seed, int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!keep || !keep_center || !keep_scale) HP3D_FAIL(ctx, HP3D_ERR_ARG, "keep / keep_center / keep_scale is NULL");
+    return masks_from_scoremap_impl(ctx, scoremap, B, H, W, K, keep, keep_center, keep_scale, mask, center, crop_size, scale, seed, valid,
+                                    area, claimed);
+}
+
+// ---- tracking several hands per frame --------------------------------------------------------------------
+int hp3d_track_hands_reset(hp3d_ctx* ctx) {
+    if (!ctx) return HP3D_ERR_ARG;
+    ctx->track_hands.ok = false;
+    ctx->track_hands.since = 0;
+    return 0;
+}
+
+int hp3d_track_hands_seed(hp3d_ctx* ctx, int B, int H, int W, int K, const float* center, const float* scale, const int32_t* valid) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!center || !scale || !valid) HP3D_FAIL(ctx, HP3D_ERR_ARG, "center / scale / valid is NULL");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    CHK(check_img(ctx, B, H, W));
+    const int n = B * K;
+    // an absent slot crops with the fall-back box an empty mask gives (mask_grow_epilogue, option "empty_reduce")
+    const float fb_c = ctx->empty_fltmax ? 0.f : 160.f, fb_s = fminf(fmaxf(256.0f / (100.f * 1.25f), 0.25f), 5.0f);
+    std::vector<float> c(center, center + (size_t)n * 2), s(scale, scale + n);
+    std::vector<int> v(n);
+    for (int b = 0; b < B; ++b) {
+        bool any = false;
+        for (int j = 0; j < K; ++j) {
+            const int i = b * K + j;
+            v[i] = valid[i] != 0 ? 1 : 0;
+            if (!v[i]) { c[i * 2] = c[i * 2 + 1] = fb_c; s[i] = fb_s; continue; }
+            any = true;
+            if (!(scale[i] > 0.f) || !std::isfinite(scale[i])) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_hands_seed: scale[%d,%d] = %g must be positive and finite", b, j, (double)scale[i]);
+            if (!std::isfinite(center[i * 2]) || !std::isfinite(center[i * 2 + 1])) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_hands_seed: center[%d,%d] is not finite", b, j);
+        }
+        if (!any) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_hands_seed: image %d has no valid slot", b);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CHK(ensure_track_hands(ctx, n));
+    TrackHandsState& T = ctx->track_hands;
+    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }
+    T.ok = false;
+    T.B = B; T.K = K; T.H = H; T.W = W;
+    HIPCHK(ctx, hipMemcpyAsync(T.center[T.cur], c.data(), sizeof(float) * (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(T.scale[T.cur], s.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(T.valid(), v.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(T.keep, v.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(T.lost(), 0, sizeof(int) * (size_t)n, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n; ++i) { T.h_flags[i] = v[i]; T.h_flags[n + i] = 0; }
+    T.ok = true; T.since = 0;
+    return 0;
+}
+
+int hp3d_track_hands_step(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* image_crop,
+                          float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop,
+                          double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area,
+                          int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return track_hands_step_impl(ctx, B, H, W, K, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false);
+}
+int hp3d_track_hands_step_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* image_crop,
+                              float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                              int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                              int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    return track_hands_step_impl(ctx, B, H, W, K, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, true);
+}
+int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
+                             float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                             int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                             int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (Hin != H || Win != W)
+        HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "tracking crops straight from the uint8 frame: the frame (%dx%d) must have the network size (%dx%d)", Hin, Win, H, W);
+    return track_hands_step_impl(ctx, B, H, W, K, nullptr, image_u8, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false);
+}
+
+int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
+                         const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
+                         float* confidence, int32_t* lost) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!keypoint_hw || !valid || !box_center || !box_scale || !center || !scale || !confidence || !lost || B < 1 || H < 1 || W < 1)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    if (!(margin >= 0.f && margin <= 16.f)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_hands_box: margin %g must be 0 (= option track_margin) or in (0, 16]", (double)margin);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t n = (size_t)B * K;
+    double* d_kp = S.upload(keypoint_hw, n * 42); NN(ctx, d_kp);
+    float* d_sm = nullptr;
+    if (score32) { d_sm = S.upload(score32, n * 32 * 32 * 21); NN(ctx, d_sm); }
+    int* d_v = S.upload((const int*)valid, n); NN(ctx, d_v);
+    float* d_bc = S.upload(box_center, n * 2); NN(ctx, d_bc);
+    float* d_bs = S.upload(box_scale, n); NN(ctx, d_bs);
+    float* d_c = S.alloc<float>(n * 2); NN(ctx, d_c);
+    float* d_s = S.alloc<float>(n); NN(ctx, d_s);
+    float* d_q = S.alloc<float>(n); NN(ctx, d_q);
+    int* d_l = S.alloc<int>(n); NN(ctx, d_l);
+    track_hands_box_launch(d_kp, d_sm, 21, (int)n, H, W, 256, margin > 0.f ? margin : ctx->track_margin, ctx->track_min_score,
+                           ctx->track_use_min_score, d_v, d_bc, d_bs, d_c, d_s, d_q, d_l, nullptr, nullptr, nullptr, nullptr, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(center, d_c, sizeof(float) * n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(scale, d_s, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(confidence, d_q, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lost, d_l, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
 
@@ -3023,6 +3368,8 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"conv_splitk_reduce_launches", &Counters::conv_splitk_reduce_launches, true},
         {"track_detect_steps", &Counters::track_detect_steps, false},
         {"track_tracked_steps", &Counters::track_tracked_steps, false},
+        {"track_hands_detect_steps", &Counters::track_hands_detect_steps, false},
+        {"track_hands_tracked_steps", &Counters::track_hands_tracked_steps, false},
         {"crop_u8_launches", &Counters::crop_u8_launches, false},
     };
     const std::string k(name);

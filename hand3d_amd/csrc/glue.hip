@@ -793,25 +793,69 @@ __device__ __forceinline__ unsigned long long mask_argmax_in(const unsigned* R, 
     return block_max_u64_all(best);
 }
 
-// slots j0 .. K-1 of image b hold no hand.  Every thread of the workgroup calls it.
-__device__ __forceinline__ void mask_absent_slots(int b, int j0, int K, int H, int W, int empty_fltmax, float* mask_out, float* center,
-                                                  float* crop_size, float* scale, int* seed_out, int* valid, int* area) {
-    for (int j = j0; j < K; ++j) {
+// slot `slot` holds no hand.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void mask_absent_slot(int slot, int H, int W, int empty_fltmax, float* mask_out, float* center, float* crop_size,
+                                                 float* scale, int* seed_out, int* valid, int* area) {
+    if (mask_out) {
+        float* mo = mask_out + (size_t)slot * H * W;
+        for (int i = threadIdx.x; i < H * W; i += blockDim.x) mo[i] = 0.f;
+    }
+    mask_grow_epilogue(nullptr, 0, slot, H, W, 0x7fffffff, -1, 0x7fffffff, -1, -1, -1, empty_fltmax, nullptr, center, crop_size, scale,
+                       seed_out);
+    if (threadIdx.x == 0) { valid[slot] = 0; area[slot] = 0; }
+}
+
+// Kept slots: on a multi-hand tracker's detect step slot j of image b with keep[b * K + j] != 0 still follows its hand
+// with the box (kc, ks); an object one of them claims is that hand, found again, and is dropped.  keep == nullptr: no kept slot.
+constexpr int MG_MAXK = 4;       // = HP3D_MAX_HANDS (include/hp3d.h)
+// The claim test, float32 op by op (a comparison with a NaN is false): the object's box centre (calc_center_bb's) lies within the
+// slot's crop window -- half = 128 / scale pixels around its centre -- or the slot's centre lies inside the object's bounding box.
+__device__ __forceinline__ bool mask_claims(float crow, float ccol, float s, int rmin, int rmax, int cmin, int cmax) {
+    const float orow = 0.5f * ((float)rmax + (float)rmin), ocol = 0.5f * ((float)cmax + (float)cmin);
+    const float half = 128.0f / s;
+    const bool near = fabsf(orow - crow) <= half && fabsf(ocol - ccol) <= half;
+    const bool inside = (float)rmin <= crow && crow <= (float)rmax && (float)cmin <= ccol && ccol <= (float)cmax;
+    return near || inside;
+}
+// the lowest kept slot of image b that claims the object, -1: none.  The same for every thread of the workgroup.
+__device__ __forceinline__ int mask_claimed_by(const int* keep, const float* kc, const float* ks, int b, int K, int rmin, int rmax, int cmin,
+                                               int cmax) {
+    if (!keep || rmax < 0) return -1;
+    for (int j = 0; j < K; ++j) {
         const int slot = b * K + j;
-        if (mask_out) {
-            float* mo = mask_out + (size_t)slot * H * W;
-            for (int i = threadIdx.x; i < H * W; i += blockDim.x) mo[i] = 0.f;
-        }
-        mask_grow_epilogue(nullptr, 0, slot, H, W, 0x7fffffff, -1, 0x7fffffff, -1, -1, -1, empty_fltmax, nullptr, center, crop_size, scale,
-                           seed_out);
-        if (threadIdx.x == 0) { valid[slot] = 0; area[slot] = 0; }
+        if (keep[slot] && mask_claims(kc[slot * 2], kc[slot * 2 + 1], ks[slot], rmin, rmax, cmin, cmax)) return j;
+    }
+    return -1;
+}
+__device__ __forceinline__ int mask_count_kept(const int* keep, int b, int K) {
+    int n = 0;
+    if (keep) for (int j = 0; j < K; ++j) n += keep[b * K + j] ? 1 : 0;
+    return n;
+}
+// the k-th free (not kept) slot of image b, in ascending order: accepted objects go to the lowest free slot first
+__device__ __forceinline__ int mask_free_slot(const int* keep, int b, int K, int k) {
+    if (!keep) return k;
+    for (int j = 0; j < K; ++j)
+        if (!keep[b * K + j] && k-- == 0) return j;
+    return K - 1;     // (not reached: the loops stop at the last free slot)
+}
+// The end of both multi-hand kernels: kept slots and the free slots behind the k filled ones come back absent; the claim counters.
+// Every thread of the workgroup calls it.
+__device__ __forceinline__ void mask_multi_finish(const int* keep, int b, int K, int k, const int* ncl, int H, int W, int empty_fltmax,
+                                                  float* mask_out, float* center, float* crop_size, float* scale, int* seed_out, int* valid,
+                                                  int* area, int* claimed) {
+    int nfree = 0;
+    for (int j = 0; j < K; ++j) {
+        const bool kept = keep && keep[b * K + j];
+        if (kept || nfree++ >= k) mask_absent_slot(b * K + j, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area);
+        if (claimed && threadIdx.x == 0) claimed[b * K + j] = ncl[j];
     }
 }
 
 HP3D_KERNEL(1024)
 void mask_grow_multi_kernel(const unsigned char* det, const float* fg, const unsigned long long* keys, int H, int W, int K, int min_area,
                             int empty_fltmax, float* mask_out, float* center, float* crop_size, float* scale, int* seed_out,
-                            int* valid, int* area) {
+                            int* valid, int* area, const int* keep, const float* keep_center, const float* keep_scale, int* claimed) {
     HP3D_DYN_SMEM(smem_f);
     const int WW = (W + 31) >> 5, P = WW + 1;
     const int NWORD = H * P;
@@ -833,12 +877,16 @@ void mask_grow_multi_kernel(const unsigned char* det, const float* fg, const uns
     if (tid == 0) { obj[-1] = 0u; obj[NWORD] = 0u; }
     __syncthreads();
     // det is empty (the global arg-max lies outside it): slot 0 is the single-hand kernel's result
-    const bool legacy = !((unsigned)sy < (unsigned)H && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+    const bool empty = !((unsigned)sy < (unsigned)H && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+    // with kept slots an empty det leaves every free slot absent: nothing is grown
+    const int nkept = mask_count_kept(keep, b, K), nfree = K - nkept;
+    const bool legacy = empty && nkept == 0;
+    int ncl[MG_MAXK] = {0, 0, 0, 0};
 
     const int nseg = (H + MG_R - 1) / MG_R, nunits = nseg * WW;
     const int num_passes = max(H, W) / 10;   // max(s[1], s[2]) // (filter_size // 2)
     int k = 0, tries = 0;
-    for (;;) {
+    for (; legacy || !empty;) {
         for (int w = tid; w < NWORD; w += nthr) {
             const int y = w / P, wx = w - y * P;
             obj[w] = (y == sy && wx == (sx >> 5)) ? (1u << (sx & 31)) : 0u;
@@ -915,25 +963,28 @@ void mask_grow_multi_kernel(const unsigned char* det, const float* fg, const uns
             atomicAdd(&s_area, cnt);
         }
         __syncthreads();
-        const int obj_area = s_area;
-        const bool accept = legacy || obj_area >= min_area;
+        const int obj_area = s_area, rmin_o = s_rmin, rmax_o = s_rmax, cmin_o = s_cmin, cmax_o = s_cmax;
+        const int claim = mask_claimed_by(keep, keep_center, keep_scale, b, K, rmin_o, rmax_o, cmin_o, cmax_o);
+        // a claimed object is dropped whatever its area; with no free slot (all kept) the others are dropped as well
+        const bool accept = claim < 0 && k < nfree && (legacy || obj_area >= min_area);
+        if (claim >= 0) ++ncl[claim];
         if (accept) {
-            const int slot = b * K + k;
-            mask_grow_epilogue(obj, P, slot, H, W, s_rmin, s_rmax, s_cmin, s_cmax, sy, sx, empty_fltmax, mask_out, center, crop_size, scale,
+            const int slot = b * K + mask_free_slot(keep, b, K, k);
+            mask_grow_epilogue(obj, P, slot, H, W, rmin_o, rmax_o, cmin_o, cmax_o, sy, sx, empty_fltmax, mask_out, center, crop_size, scale,
                                seed_out);
             if (tid == 0) { valid[slot] = legacy ? 0 : 1; area[slot] = obj_area; }
             ++k;
         }
         for (int w = tid; w < NWORD; w += nthr) detb[w] &= ~obj[w];
         ++tries;
-        if (legacy || k == K || tries == 4 * K) break;
+        if (legacy || (accept && k == nfree) || tries == 4 * K) break;
         __syncthreads();        // R is final; the box and obj have been read
         const unsigned long long key = mask_argmax_in(detb, f, W, P, NWORD);
         if (!key) break;        // nothing left
         const unsigned idx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
         sy = (int)(idx / (unsigned)W); sx = (int)(idx % (unsigned)W);
     }
-    mask_absent_slots(b, k, K, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area);
+    mask_multi_finish(keep, b, K, k, ncl, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area, claimed);
 }
 
 // The same on the per-image scratch block of mask_grow_global_kernel (mask_pack_kernel has filled det and set the first seed).  The
@@ -942,7 +993,7 @@ void mask_grow_multi_kernel(const unsigned char* det, const float* fg, const uns
 HP3D_KERNEL(1024)
 void mask_grow_multi_global_kernel(const float* fg, const unsigned long long* keys, int H, int W, int K, int min_area, int empty_fltmax,
                                    unsigned* scratch, float* mask_out, float* center, float* crop_size, float* scale, int* seed_out,
-                                   int* valid, int* area) {
+                                   int* valid, int* area, const int* keep, const float* keep_center, const float* keep_scale, int* claimed) {
     const int WW = (W + 31) >> 5, P = WW + 1;
     const int NWORD = H * P;
     const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
@@ -954,11 +1005,14 @@ void mask_grow_multi_global_kernel(const float* fg, const unsigned long long* ke
     const unsigned idx0 = 0xFFFFFFFFu - (unsigned)(keys[b] & 0xFFFFFFFFull);
     int sy = (int)(idx0 / (unsigned)W), sx = (int)(idx0 % (unsigned)W);
     const bool seed_ok = (unsigned)sy < (unsigned)H;
-    const bool legacy = !(seed_ok && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+    const bool empty = !(seed_ok && ((detb[sy * P + (sx >> 5)] >> (sx & 31)) & 1u));
+    const int nkept = mask_count_kept(keep, b, K), nfree = K - nkept;
+    const bool legacy = empty && nkept == 0;
+    int ncl[MG_MAXK] = {0, 0, 0, 0};
 
     const int num_passes = max(H, W) / 10;   // max(s[1], s[2]) // (filter_size // 2)
     int k = 0, tries = 0;
-    for (;;) {
+    for (; legacy || !empty;) {
         if (tid == 0) {
             s_box[0][0] = s_box[0][1] = sy; s_box[0][2] = s_box[0][3] = sx;     // O_0 = {seed}
             if (!seed_ok) s_box[0][1] = -1;
@@ -1048,9 +1102,11 @@ void mask_grow_multi_global_kernel(const float* fg, const unsigned long long* ke
         if (cnt) atomicAdd(&s_area, cnt);
         __syncthreads();
         const int obj_area = s_area;
-        const bool accept = legacy || obj_area >= min_area;
+        const int claim = mask_claimed_by(keep, keep_center, keep_scale, b, K, r0, r1, c0, c1);
+        const bool accept = claim < 0 && k < nfree && (legacy || obj_area >= min_area);
+        if (claim >= 0) ++ncl[claim];
         if (accept) {
-            const int slot = b * K + k;
+            const int slot = b * K + mask_free_slot(keep, b, K, k);
             mask_grow_epilogue(obj, P, slot, H, W, r0, r1, c0, c1, sy, sx, empty_fltmax, mask_out, center, crop_size, scale, seed_out);
             if (tid == 0) { valid[slot] = legacy ? 0 : 1; area[slot] = obj_area; }
             ++k;
@@ -1062,14 +1118,14 @@ void mask_grow_multi_global_kernel(const float* fg, const unsigned long long* ke
             obj[w] = 0u;
         }
         ++tries;
-        if (legacy || k == K || tries == 4 * K) break;
+        if (legacy || (accept && k == nfree) || tries == 4 * K) break;
         __syncthreads();        // R is final, obj is zero
         const unsigned long long key = mask_argmax_in(detb, f, W, P, NWORD);
         if (!key) break;        // nothing left
         const unsigned idx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
         sy = (int)(idx / (unsigned)W); sx = (int)(idx % (unsigned)W);
     }
-    mask_absent_slots(b, k, K, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area);
+    mask_multi_finish(keep, b, K, k, ncl, H, W, empty_fltmax, mask_out, center, crop_size, scale, seed_out, valid, area, claimed);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1416,13 +1472,14 @@ __device__ __forceinline__ bool finite_f32(float f) { return (__float_as_uint(f)
 // One workgroup per image.  kp_image [B,21,2] float64 (row, col) as kp_detect_kernel writes it; sm (may be null) the last 32 x 32
 // score maps with channel stride cs: confidence = mean over the 21 channels (added in channel order) of each channel's maximum
 // (NaNs never win), 0 without a map.  lost = 1 when keypoint 12 is not finite or lies outside the frame (row < 0, row > H, col < 0,
-// col > W), or -- with a threshold and a map -- when the confidence is not at least the threshold.  detected0 (may be null): zeroed
-// for the image (a tracked step's "no box of this step came from HandSegNet").
-HP3D_KERNEL(256)
-void track_box_kernel(const double* kp_image, const float* sm, int cs, int H, int W, int crop, float margin, float min_score,
-                      int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0) {
+// col > W), or -- with a threshold and a map -- when the confidence is not at least the threshold.
+struct TrackBox { float cy, cx, scale, conf; int lost; };
+// Every thread of the (256-thread) workgroup calls it; the result is thread 0's.
+__device__ __forceinline__ TrackBox track_box_rule(const double* kp_image, const float* sm, int cs, int b, int H, int W, int crop, float margin,
+                                                   float min_score, int use_min_score) {
     __shared__ float cmax[256];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
+    TrackBox r = {0.f, 0.f, 1.f, 0.f, 0};
     if (sm) {
         const int c = t & 31, g = t >> 5;
         float m = -__builtin_inff();
@@ -1464,12 +1521,69 @@ void track_box_kernel(const double* kp_image, const float* sm, int cs, int H, in
         best = best * margin;
         best = np_minimum(np_maximum(best, 50.f), 500.f);
         if (!finite_f32(best)) best = 200.f;
-        center[b * 2] = cy; center[b * 2 + 1] = cx;
-        scale[b] = np_minimum(np_maximum((float)crop / best, 1.f), 10.f);
-        confidence[b] = conf;
-        lost[b] = (!cfin || r12 < 0.f || r12 > (float)H || c12 < 0.f || c12 > (float)W ||
-                   (use_min_score && sm && !(conf >= min_score))) ? 1 : 0;
+        r.cy = cy; r.cx = cx;
+        r.scale = np_minimum(np_maximum((float)crop / best, 1.f), 10.f);
+        r.conf = conf;
+        r.lost = (!cfin || r12 < 0.f || r12 > (float)H || c12 < 0.f || c12 > (float)W ||
+                  (use_min_score && sm && !(conf >= min_score))) ? 1 : 0;
+    }
+    return r;
+}
+
+// detected0 (may be null): zeroed for the image (a tracked step's "no box of this step came from HandSegNet").
+HP3D_KERNEL(256)
+void track_box_kernel(const double* kp_image, const float* sm, int cs, int H, int W, int crop, float margin, float min_score,
+                      int use_min_score, float* center, float* scale, float* confidence, int* lost, int* detected0) {
+    const int b = blockIdx.x;
+    const TrackBox r = track_box_rule(kp_image, sm, cs, b, H, W, crop, margin, min_score, use_min_score);
+    if (threadIdx.x == 0) {
+        center[b * 2] = r.cy; center[b * 2 + 1] = r.cx;
+        scale[b] = r.scale;
+        confidence[b] = r.conf;
+        lost[b] = r.lost;
         if (detected0) detected0[b] = 0;
+    }
+}
+
+// The same per slot of the multi-hand tracker, one workgroup per slot: a slot that holds a hand (valid != 0) gets
+// track_box_kernel's box and `lost`; an absent slot holds the box it cropped with (box_center / box_scale: its fall-back box) and
+// lost = 0; the confidence is reported for both.  keep_next (may be null) = valid and not lost: the slots a detect step behind this
+// step keeps.  detected0 / area0 / claimed0 (may be null): zeroed (a tracked step).
+HP3D_KERNEL(256)
+void track_hands_box_kernel(const double* kp_image, const float* sm, int cs, int H, int W, int crop, float margin, float min_score,
+                            int use_min_score, const int* valid, const float* box_center, const float* box_scale, float* center,
+                            float* scale, float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0) {
+    const int b = blockIdx.x;
+    const TrackBox r = track_box_rule(kp_image, sm, cs, b, H, W, crop, margin, min_score, use_min_score);
+    if (threadIdx.x == 0) {
+        const bool v = valid[b] != 0;
+        center[b * 2] = v ? r.cy : box_center[b * 2];
+        center[b * 2 + 1] = v ? r.cx : box_center[b * 2 + 1];
+        scale[b] = v ? r.scale : box_scale[b];
+        confidence[b] = r.conf;
+        lost[b] = v ? r.lost : 0;
+        if (keep_next) keep_next[b] = (v && !r.lost) ? 1 : 0;
+        if (detected0) detected0[b] = 0;
+        if (area0) area0[b] = 0;
+        if (claimed0) claimed0[b] = 0;
+    }
+}
+
+// A multi-hand detect step's choice per slot: a kept slot holds its tracked box (detected = 0, valid = 1, area = 0); any other takes what
+// the claimed growth wrote for it -- a newly found hand (detected = valid = 1, its box and pixel count) or nothing (valid = 0, area = 0,
+// the fall-back box).
+HP3D_KERNEL(256)
+void track_hands_select_kernel(const int* keep, const float* det_center, const float* det_scale, const int* det_valid, const int* det_area,
+                               int n, float* box_center, float* box_scale, int* valid, int* detected, int* area) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (keep[i]) {
+            valid[i] = 1; detected[i] = 0; area[i] = 0;
+        } else {
+            const int v = det_valid[i] != 0 ? 1 : 0;
+            box_center[i * 2] = det_center[i * 2]; box_center[i * 2 + 1] = det_center[i * 2 + 1];
+            box_scale[i] = det_scale[i];
+            valid[i] = v; detected[i] = v; area[i] = v ? det_area[i] : 0;
+        }
     }
 }
 
@@ -1615,13 +1729,15 @@ void mask_grow_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltm
 }
 // B images, K slots each: outputs at index b * K + j.  scratch: null = the LDS kernel, else B x mask_grow_global_words(H, W) words
 void mask_grow_multi_launch(const MaskBuffers& mb, int B, int H, int W, int K, int min_area, int empty_fltmax, unsigned* scratch,
-                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s) {
+                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s,
+                            const MaskKeep& mk) {
     if (scratch) {
         const long nword = (long)H * ((W + 31) / 32 + 1);
         HP3D_LAUNCH(mask_pack_kernel, dim3(grid_for(nword, 256, 64), B), dim3(256), 0, s, (const unsigned char*)mb.det,
                     (const unsigned long long*)mb.argmax_key, H, W, scratch);
         HP3D_LAUNCH(mask_grow_multi_global_kernel, dim3(B), dim3(1024), 0, s, (const float*)mb.fg, (const unsigned long long*)mb.argmax_key,
-                    H, W, K, min_area, empty_fltmax, scratch, mask_out, center, crop_size, scale, seed, valid, area);
+                    H, W, K, min_area, empty_fltmax, scratch, mask_out, center, crop_size, scale, seed, valid, area, mk.keep, mk.center, mk.scale,
+                    mk.claimed);
         return;
     }
     const size_t smem = mask_grow_lds_bytes(H, W);
@@ -1631,7 +1747,8 @@ void mask_grow_multi_launch(const MaskBuffers& mb, int B, int H, int W, int K, i
         //  256 bytes, and mask_grow_lds_fits admits maps of at most 160 KB - 1 KB)
         (void)hipFuncSetAttribute((const void*)mask_grow_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
     HP3D_LAUNCH(mask_grow_multi_kernel, dim3(B), dim3(1024), smem, s, (const unsigned char*)mb.det, (const float*)mb.fg,
-                (const unsigned long long*)mb.argmax_key, H, W, K, min_area, empty_fltmax, mask_out, center, crop_size, scale, seed, valid, area);
+                (const unsigned long long*)mb.argmax_key, H, W, K, min_area, empty_fltmax, mask_out, center, crop_size, scale, seed, valid, area,
+                mk.keep, mk.center, mk.scale, mk.claimed);
 }
 size_t fc_scratch_floats(int B, int Cin, int Cout) { return (size_t)((Cin + FC_KCH - 1) / FC_KCH) * B * Cout; }
 void fc_launch(const float* x, int B, int Cin, int x_stride, const float* w, const float* bias, int Cout, int act,
@@ -1687,6 +1804,17 @@ void track_select_launch(const int* lost_prev, const float* det_center, const fl
                          float* box_center, float* box_scale, int* detected, hipStream_t s) {
     HP3D_LAUNCH(track_select_kernel, dim3(grid_for(B)), dim3(256), 0, s, lost_prev, det_center, det_scale, B, force_all, box_center,
                 box_scale, detected);
+}
+void track_hands_box_launch(const double* kp_image, const float* sm, int cs, int n, int H, int W, int crop, float margin, float min_score,
+                            int use_min_score, const int* valid, const float* box_center, const float* box_scale, float* center, float* scale,
+                            float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0, hipStream_t s) {
+    HP3D_LAUNCH(track_hands_box_kernel, dim3(n), dim3(256), 0, s, kp_image, sm, cs, H, W, crop, margin, min_score, use_min_score, valid,
+                box_center, box_scale, center, scale, confidence, lost, keep_next, detected0, area0, claimed0);
+}
+void track_hands_select_launch(const int* keep, const float* det_center, const float* det_scale, const int* det_valid, const int* det_area,
+                               int n, float* box_center, float* box_scale, int* valid, int* detected, int* area, hipStream_t s) {
+    HP3D_LAUNCH(track_hands_select_kernel, dim3(grid_for(n)), dim3(256), 0, s, keep, det_center, det_scale, det_valid, det_area, n,
+                box_center, box_scale, valid, detected, area);
 }
 void argmax2d_launch(const float* x, int B, int H, int W, int C, int cs, int* out_rc, hipStream_t s) {
     HP3D_LAUNCH(argmax2d_kernel, dim3(C, B), dim3(256), 0, s, x, H, W, C, cs, out_rc);

@@ -448,8 +448,25 @@ size_t mask_grow_global_words(int H, int W);     // per-image scratch of mask_gr
 void mask_grow_global_launch(const MaskBuffers& mb, int B, int H, int W, int empty_fltmax, unsigned* scratch, float* mask_out,
                              float* center, float* crop_size, float* scale, int* seed, hipStream_t s);
 // up to K hands per image: outputs [B,K,...]; needs mb.fg; scratch null = bitmaps in LDS, else as mask_grow_global_launch
+// mk: slots a multi-hand tracker still follows -- keep [B,K] (!= 0: kept), their boxes center [B,K,2] / scale [B,K]; an
+// object a kept slot claims is dropped and counted in claimed [B,K]; kept slots come back as absent ones.  keep == nullptr: none.
+struct MaskKeep {
+    const int* keep = nullptr;
+    const float* center = nullptr;
+    const float* scale = nullptr;
+    int* claimed = nullptr;
+};
 void mask_grow_multi_launch(const MaskBuffers& mb, int B, int H, int W, int K, int min_area, int empty_fltmax, unsigned* scratch,
-                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s);
+                            float* mask_out, float* center, float* crop_size, float* scale, int* seed, int* valid, int* area, hipStream_t s,
+                            const MaskKeep& mk = MaskKeep());
+// the multi-hand tracker, n = B * K slots: track_box per slot with valid gating (an absent slot holds box_center /
+// box_scale and lost = 0; keep_next = valid and not lost; detected0 / area0 / claimed0, may be null, are zeroed); a detect step's per-slot choice
+// between the kept box and what the claimed growth wrote
+void track_hands_box_launch(const double* kp_image, const float* sm, int cs, int n, int H, int W, int crop, float margin, float min_score,
+                            int use_min_score, const int* valid, const float* box_center, const float* box_scale, float* center, float* scale,
+                            float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0, hipStream_t s);
+void track_hands_select_launch(const int* keep, const float* det_center, const float* det_scale, const int* det_valid, const int* det_area,
+                               int n, float* box_center, float* box_scale, int* valid, int* detected, int* area, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

@@ -168,6 +168,25 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
+    def track_hands(self, image, hand_side, max_hands):
+        """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
+            keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
+            A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
+            when a followed hand was lost, when a frame has no hand to follow, or on the `track_redetect` schedule; a detect step
+            keeps the slots that still follow a hand and fills the free ones with the objects none of them claims.
+            `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3]; `hand_side` [B,K,2], one row per slot.
+            Returns track()'s tuple with a K axis plus valid [B,K] (0: the slot holds no hand) and area [B,K] (pixels of the
+            object where detected = 1).  The engine's `claimed` counters (objects a kept slot claimed on a detect step) are not in the
+            tuple: Engine.track_hands_step returns them. """
+        step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step
+        o = step(image, hand_side, max_hands)
+        return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],
+                o['detected'], o['valid'], o['area'])
+
+    def track_hands_reset(self):
+        """ The next track_hands() call detects anew and keeps no slot. """
+        self.engine.track_hands_reset()
+
     def inference2d_keypoints(self, image):
         """ inference2d() + detect_keypoints + trafo_coords on the device (eval2d.py:58,93-94): keypoint_hw [B,21,2]
             float64 in the input image, keypoint_hw_crop [B,21,2] float64, scale_crop, center. """

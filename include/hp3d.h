@@ -151,7 +151,8 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            (ColorHandPose3DNetwork.py:84): a policy choice for the hand's motion between frames, not a measurement;
  *          "track_min_score" = "off" (default) | a number: a tracked image counts as lost when its confidence is below it.  A useful
  *                            value depends on the trained weights: callers calibrate it on the confidence the steps return;
- *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image;
+ *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image
+ *                            (hp3d_track_hands_step*: that fills free slots only, kept slots are not re-boxed);
  *          "hands_min_area" = "0" (default: off) | N: hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer than N pixels
  *                            instead of reporting them as hands.  A useful value depends on the trained weights: callers calibrate it on
  *                            the `area` every call returns;
@@ -358,6 +359,53 @@ int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* i
                         float* keypoint_coord3d, float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid,
                         int32_t* area);
 
+/* ---- tracking several hands per frame -----------------------------------------
+ * K slots per frame, 1 <= K <= HP3D_MAX_HANDS; every per-hand array is [B,K,...] at index b * K + j.  A slot follows its hand for as
+ * long as it is not lost, so the slot index is the hand's identity from frame to frame.  The state is separate from hp3d_track_step*'s.
+ * A step is a DETECT step -- the first one after hp3d_create / hp3d_track_hands_reset / a change of (B, K, H, W); when the previous step
+ * flagged a valid slot as lost; when some image has no valid slot; with option "track_redetect" = N > 0 every N-th step -- or a TRACKED
+ * step (no HandSegNet, no soft-max, no mask growth, no HandSegNet weights needed): the K crops of a frame come from the state's boxes.
+ * The whole batch detects together.  On a detect step the slots that are valid and not lost are KEPT: they crop with their tracked box
+ * (detected = 0), also on a scheduled re-detection.  The objects of the detection map are found as hp3d_infer_hands finds them; an
+ * object is CLAIMED by a kept slot with box (c, s), half = 128 / s, when its bounding-box centre o has |o.row - c.row| <= half and
+ * |o.col - c.col| <= half, or when c lies inside its bounding box (float32; a comparison with a NaN is false).  A claimed object is that
+ * slot's hand found again: it is dropped (never tested against "hands_min_area") and counted for the lowest slot that claims it.  The
+ * others fill the free slots in the order of discovery, lowest free slot first (detected = valid = 1, box and area as hp3d_infer_hands
+ * gives them); free slots left over are absent (valid = 0, area = 0, the fall-back box of option "empty_reduce").  Every growth, claimed
+ * or not, counts toward the cap of 4 K growths per image.  Absent slots run the back half on their fall-back crop; their confidence is
+ * reported, their lost flag is 0, and they keep that box until a detect step fills them.
+ * hp3d_track_hands_reset   the next step detects and keeps nothing.
+ * hp3d_track_hands_seed    center [B,K,2] (row, col), scale [B,K], valid int32 [B,K]: valid slots need a finite centre and a finite
+ *                          scale > 0, every image at least one valid slot (HP3D_ERR_ARG otherwise); the next step at (B, K, H, W) is a
+ *                          tracked one.
+ * hp3d_track_hands_step    as hp3d_track_step with hand_side [B,K,2] and every output per slot, plus valid int32 [B,K], area int32 [B,K]
+ *                          (the object's pixel count where detected = 1, else 0) and claimed int32 [B,K] (objects the slot claimed on
+ *                          this step; 0 on a tracked step).  For a valid slot the next box, confidence and lost are hp3d_track_box's.
+ * hp3d_track_hands_step_dev / _u8   as hp3d_track_step_dev / hp3d_track_step_u8.
+ * hp3d_track_hands_box (per-op) hp3d_track_box per slot with valid gating: keypoint_hw [B,K,21,2], score32 [B,K,32,32,21] or NULL,
+ *                          valid [B,K], the boxes the slots cropped with box_center [B,K,2] / box_scale [B,K] -> center, scale,
+ *                          confidence, lost: hp3d_track_box's for a valid slot; an absent one holds its box with lost = 0.
+ * Outputs may be NULL as for hp3d_track_step.  K outside 1 ... HP3D_MAX_HANDS or a NULL image / hand_side -> HP3D_ERR_ARG before any
+ * launch.  Options "track_margin", "track_min_score", "track_redetect", "hands_min_area", "mask_grow", "empty_reduce" apply; batches
+ * run in chunks of at most micro_batch / K frames on one stream; no graph replay.                                                  */
+int hp3d_track_hands_reset(hp3d_ctx* ctx);
+int hp3d_track_hands_seed(hp3d_ctx* ctx, int B, int H, int W, int K, const float* center, const float* scale, const int32_t* valid);
+int hp3d_track_hands_step(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* image_crop,
+                          float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop,
+                          double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area,
+                          int32_t* claimed);
+int hp3d_track_hands_step_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* image_crop,
+                              float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                              int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                              int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
+                             float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                             int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                             int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
+                         const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
+                         float* confidence, int32_t* lost);
+
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65
  *                      x [B,H,W,Cin], w HWIO, SAME padding incl. the asymmetric stride-2 case.
@@ -380,6 +428,12 @@ int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* i
  * hp3d_masks_from_scoremap the mask stage of hp3d_infer_hands: scoremap [B,H,W,2], K -> mask [B,K,H,W], center [B,K,2],
  *                      crop_size [B,K], scale [B,K], seed int32 [B,K,2] ((-1, -1) for an absent slot), valid [B,K], area [B,K] int32;
  *                      same size limits and "mask_grow" forms as hp3d_mask_from_scoremap
+ * hp3d_masks_from_scoremap_keep the mask stage of a multi-hand tracker's detect step (see hp3d_track_hands_step): keep int32 [B,K]
+ *                      (!= 0: the slot is kept), keep_center [B,K,2], keep_scale [B,K] -> the outputs of hp3d_masks_from_scoremap with
+ *                      accepted objects in the free slots and kept slots coming back as absent ones, plus claimed int32 [B,K].  With
+ *                      no kept slot in an image its result is hp3d_masks_from_scoremap's bit for bit; with kept slots and an empty
+ *                      detection map every free slot is absent; with no free slot the growth still runs to the end of the map or the
+ *                      cap, so that claimed tells which kept slots HandSegNet still sees.
  * hp3d_fc              NetworkOps.fully_connected(_relu)                      utils/general.py:112-136
  * hp3d_argmax2d        detect_keypoints (per-channel first arg-max)           utils/general.py:331-344
  *                      x [B,H,W,C] -> int32 [B,C,2] (row, col)                                    */
@@ -396,6 +450,9 @@ int hp3d_mask_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, 
                             float* mask, float* center, float* crop_size, float* scale, int32_t* seed);
 int hp3d_masks_from_scoremap(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, float* mask, float* center,
                              float* crop_size, float* scale, int32_t* seed, int32_t* valid, int32_t* area);
+int hp3d_masks_from_scoremap_keep(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, const int32_t* keep,
+                                  const float* keep_center, const float* keep_scale, float* mask, float* center, float* crop_size,
+                                  float* scale, int32_t* seed, int32_t* valid, int32_t* area, int32_t* claimed);
 int hp3d_fc(hp3d_ctx* ctx, const float* x, int B, int Cin, const float* w, const float* bias,
             int Cout, int act, float* out);
 int hp3d_argmax2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C, int32_t* out_rc);
@@ -426,7 +483,8 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "first_touch_launches" = read passes in front of conv1_1 (option "first_touch");
  * "mask_grow_global_launches" = mask growths (one launch per call or chunk, all its images) on the global-scratch kernel (option "mask_grow");
  * "track_detect_steps" / "track_tracked_steps" = hp3d_track_step* calls that ran HandSegNet / that cropped from the previous step's keypoints;
- * "crop_u8_launches" = crops taken straight from a uint8 frame (hp3d_track_step_u8's tracked steps, one per chunk; hp3d_crop_and_resize_u8);
+ * "track_hands_detect_steps" / "track_hands_tracked_steps" = the same for hp3d_track_hands_step*;
+ * "crop_u8_launches" = crops taken straight from a uint8 frame (tracked steps of hp3d_track_step_u8 / hp3d_track_hands_step_u8, one per chunk; hp3d_crop_and_resize_u8);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
