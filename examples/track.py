@@ -7,6 +7,7 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py frames.npy                   (uint8 or float [N,H,W,3])
     python examples/track.py --synthetic                  (seeded synthetic weights + frames)
     python examples/track.py --synthetic --hands 2        (up to K hands per frame, each in its own slot: DESIGN.md 4.13)
+    python examples/track.py video_hd.npy --detect-scale 4   (detect on the 4 x 4 area mean, crop from the frame: DESIGN.md 4.14)
 """
 import glob
 import json
@@ -23,6 +24,8 @@ if __name__ == '__main__':
     ap.add_argument('--redetect', type=int, default=0, help='every N-th frame detects anew (0: only when the hand is lost)')
     ap.add_argument('--hands', type=int, default=0, metavar='K',
                     help='follow up to K hands per frame, each in its own slot (0: the single-hand tracker)')
+    ap.add_argument('--detect-scale', type=int, default=1, metavar='F', choices=range(1, 9),
+                    help='detect steps find the hand on the F x F area mean of the frame and crop from the frame itself (1: detect on the frame)')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -51,6 +54,7 @@ if __name__ == '__main__':
             frames = [np.asarray(Image.open(p).convert('RGB')) for p in paths]
     net.engine.set_option('track_redetect', str(a.redetect))
     net.engine.set_option('track_min_score', a.min_score)
+    net.engine.set_option('detect_scale', str(a.detect_scale))
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
     net.track_reset()
     net.track_hands_reset()

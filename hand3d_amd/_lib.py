@@ -77,6 +77,10 @@ _SIGNATURES = {
     'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
     'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
     'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'hp3d_downscale': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_downscale_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_boxes_to_frame': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'hp3d_boxes_to_detect': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'hp3d_mask_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'hp3d_fc': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_argmax2d': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -566,6 +570,41 @@ class Engine(object):
         out = np.empty((B, crop_size, crop_size, 3), np.float32)
         self._chk(self.lib.hp3d_crop_and_resize_u8(self.h, _ptr(img), B, H, W, _ptr(center), _ptr(scale), crop_size, _ptr(out)))
         return out
+
+    # -- detection on a reduced frame (include/hp3d.h): the per-op forms ----------------
+    def downscale(self, image, f):
+        """The detection frame of float32 frames [B,H,W,3]: the f x f area mean [B,ceil(H/f),ceil(W/f),3] (clipped windows)."""
+        image = _f32(image)
+        assert image.ndim == 4 and image.shape[3] == 3, "image must be [B,H,W,3]"
+        B, H, W, _ = image.shape
+        out = np.empty((B, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
+        self._chk(self.lib.hp3d_downscale(self.h, _ptr(image), B, H, W, int(f), _ptr(out)))
+        return out
+
+    def downscale_u8(self, image_u8, f):
+        """downscale of uint8 frames [B,H,W,3], normalised (mean / 255 - 0.5) from the exact integer window sums."""
+        img = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        assert img.ndim == 4 and img.shape[3] == 3, "image must be [B,H,W,3] uint8"
+        B, H, W, _ = img.shape
+        out = np.empty((B, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
+        self._chk(self.lib.hp3d_downscale_u8(self.h, _ptr(img), B, H, W, int(f), _ptr(out)))
+        return out
+
+    def boxes_to_frame(self, center_d, crop_size_d, f):
+        """Detection-frame boxes (center_d [...,2], crop_size_d [...]) in frame coordinates: (center, crop_size, scale)."""
+        cd, sd = _f32(center_d), _f32(crop_size_d)
+        assert cd.shape == sd.shape + (2,), "center_d must be [...,2], crop_size_d [...]"
+        center, size, scale = np.empty_like(cd), np.empty_like(sd), np.empty_like(sd)
+        self._chk(self.lib.hp3d_boxes_to_frame(self.h, sd.size, int(f), _ptr(cd), _ptr(sd), _ptr(center), _ptr(size), _ptr(scale)))
+        return center, size, scale
+
+    def boxes_to_detect(self, center, scale, f):
+        """Frame boxes (center [...,2], scale [...]) in detection-frame coordinates: (center_d, scale_d)."""
+        c, s = _f32(center), _f32(scale)
+        assert c.shape == s.shape + (2,), "center must be [...,2], scale [...]"
+        cd, sd = np.empty_like(c), np.empty_like(s)
+        self._chk(self.lib.hp3d_boxes_to_detect(self.h, s.size, int(f), _ptr(c), _ptr(s), _ptr(cd), _ptr(sd)))
+        return cd, sd
 
     def infer_2d(self, image):
         image = _f32(image)

@@ -280,6 +280,8 @@ struct Options {
     int track_use_min_score = 0;    // ... "off" (default): never
     int track_redetect = 0;         // option "track_redetect": every N-th tracking step is a detect step that re-boxes every image (0: never)
     int hands_min_area = 0;         // option "hands_min_area": hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer pixels (0: off)
+    int detect_scale = 1;           // option "detect_scale": the detect steps of hp3d_track_step* / hp3d_track_hands_step* find the hand on the frame's
+                                    // f x f area mean and crop from the frame itself (1: detect on the frame)
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -308,6 +310,7 @@ struct Counters {
     long track_detect_steps = 0, track_tracked_steps = 0;      // hp3d_track_step*: steps that ran HandSegNet / that did not
     long crop_u8_launches = 0;                      // crops taken straight from a uint8 frame (crop_and_resize_u8_kernel)
     long track_hands_detect_steps = 0, track_hands_tracked_steps = 0;      // hp3d_track_hands_step*: as track_*_steps
+    long detect_scale_steps = 0;                    // detect steps of either tracker that ran at detect_scale > 1
 };
 
 // What a context knows about the hands it follows (hp3d_track_*): the boxes for the next step, on the device, and the host's copy of the
@@ -325,6 +328,7 @@ struct TrackState {
     int cur = 0;
     bool valid = false;                 // box[cur] holds boxes for (B, H, W)
     int B = 0, H = 0, W = 0;
+    int f = 1;                          // ... found at this detect_scale (a change counts as a change of shape)
     int since = 0;                      // tracked steps since the last detect step
 };
 
@@ -343,6 +347,7 @@ struct TrackHandsState {
     int cur = 0;
     bool ok = false;                    // box[cur] and the flags hold a state for (B, K, H, W)
     int B = 0, K = 0, H = 0, W = 0;
+    int f = 1;                          // the detect_scale of that state (a change counts as a change of shape)
     int since = 0;                      // tracked steps since the last detect step
     int* valid() const { return flags; }
     int* lost() const { return flags + (size_t)B * K; }
@@ -376,6 +381,9 @@ struct hp3d_ctx : Options, Counters {
           *d_segsmall = nullptr, *d_concat = nullptr, *d_sm[3] = {nullptr, nullptr, nullptr}, *d_can = nullptr,
           *d_rot = nullptr, *d_u = nullptr, *d_fc1 = nullptr, *d_fc2 = nullptr, *d_fg = nullptr,
           *d_pooled = nullptr, *d_fcpart = nullptr;
+    float* d_stage = nullptr;            // detect_scale > 1: a host float32 frame at full size (d_image holds the detection frame)
+    size_t stage_floats = 0;
+    float *d_keepc = nullptr, *d_keeps = nullptr;      // detect_scale > 1: the kept slots' boxes in detection-frame coordinates
     hipStream_t copy_stream = nullptr;   // hp3d_upload_async: H2D of the next batch under the current batch's kernels
     hipEvent_t upload_done = nullptr;
     double* d_kpimg = nullptr;   // [B,21,2] float64 (trafo_coords of the detected keypoints)
@@ -602,6 +610,8 @@ int ensure_arena(hp3d_ctx* ctx, int B, int H, int W, int slots = 0) {
         CHK(dev_realloc(ctx, &ctx->d_valid, (size_t)B));
         CHK(dev_realloc(ctx, &ctx->d_area, (size_t)B));
         CHK(dev_realloc(ctx, &ctx->d_keys, (size_t)B));
+        CHK(dev_realloc(ctx, &ctx->d_keepc, (size_t)B * 2));
+        CHK(dev_realloc(ctx, &ctx->d_keeps, (size_t)B));
         ctx->capB = B;
         ctx->sideB = B;
     }
@@ -1755,6 +1765,48 @@ void track_free(hp3d_ctx* ctx) {
     T = TrackState();
 }
 
+// Option "detect_scale" = f > 1: a detect step of either tracker finds the hand on the [Hd, Wd] = [ceil(H / f),
+// ceil(W / f)] area mean of the frame -- HandSegNet, the soft-max and the mask growth run there exactly as they run on a frame of that
+// size -- maps the boxes to frame coordinates and crops from the frame itself.  The arena and the chunking follow (Hd, Wd); a host
+// float32 frame is staged in a buffer of its own (d_image holds the detection frame).  f = 1: (Hd, Wd) = (H, W), nothing changes.
+int detect_frame(hp3d_ctx* ctx, int H, int W, int* Hd, int* Wd) {
+    const int f = ctx->detect_scale;
+    *Hd = (H + f - 1) / f; *Wd = (W + f - 1) / f;
+    if (f > 1 && (*Hd < 16 || *Wd < 16))
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "detect_scale=%d: the detection frame of a %dx%d frame is %dx%d (need >= 16x16)", f, H, W, *Hd, *Wd);
+    return 0;
+}
+int ensure_stage(hp3d_ctx* ctx, size_t floats) {
+    if (floats > ctx->stage_floats) {
+        CHK(dev_realloc(ctx, &ctx->d_stage, floats));
+        ctx->stage_floats = floats;
+    }
+    return 0;
+}
+// the front of such a detect step: the detection frame into d_image, detection at (nb, Hd, Wd), the boxes of `slots` slots to the frame
+int run_detect_reduced(hp3d_ctx* ctx, const float* d_img, const unsigned char* d_u8, int nb, int H, int W, int Hd, int Wd, int K = 0,
+                       const MaskKeep& mk = MaskKeep()) {
+    const int f = ctx->detect_scale, slots = nb * std::max(K, 1);
+    {
+        const double px = (double)nb * H * W * 3;
+        ProfScope ps(ctx, d_u8 ? "downscale_u8" : "downscale", d_u8 ? "downscale_u8" : "downscale", 0.0, px * (d_u8 ? 1.0 : 4.0) + 4.0 * nb * Hd * Wd * 3);
+        if (d_u8) downscale_u8_launch(d_u8, nb, H, W, f, ctx->d_image, ctx->stream);
+        else downscale_launch(d_img, nb, H, W, f, ctx->d_image, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    MaskKeep mkd = mk;
+    if (K > 0 && mk.keep) {
+        ProfScope ps(ctx, "box_to_detect", "box_to_detect", 0.0, 24.0 * slots);
+        box_to_detect_launch(mk.center, mk.scale, slots, f, ctx->d_keepc, ctx->d_keeps, ctx->stream);
+        mkd.center = ctx->d_keepc; mkd.scale = ctx->d_keeps;
+    }
+    CHK(run_detect_and_crop(ctx, ctx->d_image, nb, Hd, Wd, 0, true, false, K, mkd));
+    ProfScope ps(ctx, "box_to_frame", "box_to_frame", 0.0, 28.0 * slots);
+    box_to_frame_launch(ctx->d_center, ctx->d_cropsize, slots, f, ctx->d_center, ctx->d_cropsize, ctx->d_scale, ctx->stream);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 // One step of a video: a DETECT step (HandSegNet -> mask -> box for the whole batch, then per image the tracked box where it is
 // still good) or a TRACKED step (no HandSegNet, no soft-max, no mask growth: the crop comes from the boxes the previous step
 // derived from its keypoints).  Behind the crop both are infer_full_impl: PoseNet2D, the lifting stage, keypoint detection -- plus
@@ -1769,10 +1821,13 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
                     double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev) {
     if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     CHK(check_img(ctx, B, H, W));
+    int Hd, Wd;
+    CHK(detect_frame(ctx, H, W, &Hd, &Wd));
+    const int f = ctx->detect_scale;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TrackState& T = ctx->track;
     if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
-    const bool fresh = !T.valid || T.B != B || T.H != H || T.W != W;
+    const bool fresh = !T.valid || T.B != B || T.H != H || T.W != W || T.f != f;
     bool any_lost = false;
     if (!fresh)
         for (int b = 0; b < B; ++b) any_lost = any_lost || T.h_lost[b] != 0;
@@ -1780,9 +1835,10 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     const bool detect = fresh || any_lost || sched;
     const int force_all = (fresh || sched) ? 1 : 0;      // nothing to keep / a scheduled re-detection re-boxes every image
     CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
-    const int mb0 = auto_micro_batch(ctx, B, H, W);
+    const int mb0 = auto_micro_batch(ctx, B, Hd, Wd);
     const int mb = mb0 <= 0 ? B : std::min(mb0, B);
-    CHK(ensure_arena(ctx, mb, H, W));
+    CHK(ensure_arena(ctx, mb, Hd, Wd));
+    if (f > 1 && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track(ctx, B));
     T.valid = false;                                     // a step that fails half way leaves no boxes behind
     if (image_u8) {
@@ -1803,11 +1859,29 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
         if (!dev) {
             CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * 2, false));
             d_hs = ctx->d_hs;
-            if (!image_u8) { CHK(copy_in(ctx, ctx->d_image, d_img, (size_t)nb * H * W * 3, false)); d_img = ctx->d_image; }
+            if (!image_u8) {
+                float* stage = f > 1 ? ctx->d_stage : ctx->d_image;
+                CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
+                d_img = stage;
+            }
         }
         float* bc = T.center[cur] + (size_t)b0 * 2;
         float* bs = T.scale[cur] + b0;
-        if (detect) {
+        if (detect && f > 1) {
+            CHK(run_detect_reduced(ctx, d_img, d_u8, nb, H, W, Hd, Wd));
+            {
+                ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
+                track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
+            }
+            if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
+                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
+                crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
+                ++ctx->crop_u8_launches;
+            } else {
+                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
+                crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
+            }
+        } else if (detect) {
             if (image_u8) {
                 ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
                 preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
@@ -1863,9 +1937,10 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     HIPCHK(ctx, hipMemcpyAsync(T.h_lost, T.lost, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipEventRecord(T.ev_lost, ctx->stream));
     T.pending = true;
-    T.cur = nxt; T.valid = true; T.B = B; T.H = H; T.W = W;
+    T.cur = nxt; T.valid = true; T.B = B; T.H = H; T.W = W; T.f = f;
     T.since = detect ? 0 : T.since + 1;
     ++(detect ? ctx->track_detect_steps : ctx->track_tracked_steps);
+    if (detect && f > 1) ++ctx->detect_scale_steps;
     if (!dev) return finish_op(ctx);
     return 0;
 }
@@ -2008,11 +2083,14 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
     CHK(check_img(ctx, B, H, W));
+    int Hd, Wd;
+    CHK(detect_frame(ctx, H, W, &Hd, &Wd));
+    const int f = ctx->detect_scale;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TrackHandsState& T = ctx->track_hands;
     if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
     const int n = B * K;
-    const bool fresh = !T.ok || T.B != B || T.K != K || T.H != H || T.W != W;
+    const bool fresh = !T.ok || T.B != B || T.K != K || T.H != H || T.W != W || T.f != f;
     bool any_lost = false, no_hand = false;      // a valid slot was lost / an image has nothing to follow
     if (!fresh)
         for (int b = 0; b < B; ++b) {
@@ -2027,13 +2105,14 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     const bool sched = ctx->track_redetect > 0 && T.since + 1 >= ctx->track_redetect;
     const bool detect = fresh || any_lost || no_hand || sched;
     CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
-    const int front = auto_micro_batch(ctx, B, H, W), back = auto_micro_batch(ctx, n, 256, 256);
+    const int front = auto_micro_batch(ctx, B, Hd, Wd), back = auto_micro_batch(ctx, n, 256, 256);
     int mb = front <= 0 ? B : std::min(front, B);
     if (back > 0) mb = std::min(mb, std::max(1, back / K));
-    CHK(ensure_arena(ctx, mb, H, W, mb * K));
+    CHK(ensure_arena(ctx, mb, Hd, Wd, mb * K));
+    if (f > 1 && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track_hands(ctx, n));
     T.ok = false;                                        // a step that fails half way leaves no state behind
-    T.B = B; T.K = K; T.H = H; T.W = W;                  // (the flags' layout: lost() = flags + B K)
+    T.B = B; T.K = K; T.H = H; T.W = W; T.f = f;         // (the flags' layout: lost() = flags + B K)
     if (fresh) HIPCHK(ctx, hipMemsetAsync(T.keep, 0, sizeof(int) * (size_t)n, ctx->stream));      // nothing to keep
     if (image_u8) {
         const size_t nbytes = (size_t)B * H * W * 3;
@@ -2054,11 +2133,32 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
         if (!dev) {
             CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false));
             d_hs = ctx->d_hs;
-            if (!image_u8) { CHK(copy_in(ctx, ctx->d_image, d_img, (size_t)nb * H * W * 3, false)); d_img = ctx->d_image; }
+            if (!image_u8) {
+                float* stage = f > 1 ? ctx->d_stage : ctx->d_image;
+                CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
+                d_img = stage;
+            }
         }
         float* bc = T.center[cur] + s0 * 2;
         float* bs = T.scale[cur] + s0;
-        if (detect) {
+        if (detect && f > 1) {
+            MaskKeep mk;
+            mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
+            CHK(run_detect_reduced(ctx, d_img, d_u8, nb, H, W, Hd, Wd, K, mk));
+            {
+                ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
+                track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
+                                          T.detected + s0, T.area + s0, ctx->stream);
+            }
+            if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
+                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
+                crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+                ++ctx->crop_u8_launches;
+            } else {
+                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
+                crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+            }
+        } else if (detect) {
             if (image_u8) {
                 ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
                 preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
@@ -2126,6 +2226,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     T.cur = nxt; T.ok = true;
     T.since = detect ? 0 : T.since + 1;
     ++(detect ? ctx->track_hands_detect_steps : ctx->track_hands_tracked_steps);
+    if (detect && f > 1) ++ctx->detect_scale_steps;
     if (!dev) return finish_op(ctx);
     return 0;
 }
@@ -2257,7 +2358,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
                     &ctx->d_crop, &ctx->d_center, &ctx->d_scale, &ctx->d_cropsize, &ctx->d_kpmap, &ctx->d_coord,
                     &ctx->d_mask, &ctx->d_segsmall, &ctx->d_concat, &ctx->d_sm[0], &ctx->d_sm[1], &ctx->d_sm[2],
                     &ctx->d_can, &ctx->d_rot, &ctx->d_u, &ctx->d_fc1, &ctx->d_fc2, &ctx->d_fg,
-                    &ctx->d_pooled, &ctx->d_fcpart};
+                    &ctx->d_pooled, &ctx->d_fcpart, &ctx->d_stage, &ctx->d_keepc, &ctx->d_keeps};
     for (float** p : fp)
         if (*p) hipFree(*p);
     if (ctx->d_kpimg) hipFree(ctx->d_kpimg);
@@ -2436,6 +2537,11 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
         const long n = strtol(value, &end, 10);
         if (end == value || *end || n < 0 || n > (1L << 30)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "hands_min_area wants a non-negative integer (0 = off), got %s", value);
         ctx->hands_min_area = (int)n;
+        return 0;
+    }
+    if (k == "detect_scale") {
+        if (v.size() != 1 || v[0] < '1' || v[0] > '8') HP3D_FAIL(ctx, HP3D_ERR_ARG, "detect_scale wants an integer in 1 ... 8, got %s", value);
+        ctx->detect_scale = v[0] - '0';
         return 0;
     }
     if (k == "track_redetect") {
@@ -2836,7 +2942,7 @@ int hp3d_track_hands_seed(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     TrackHandsState& T = ctx->track_hands;
     if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }
     T.ok = false;
-    T.B = B; T.K = K; T.H = H; T.W = W;
+    T.B = B; T.K = K; T.H = H; T.W = W; T.f = ctx->detect_scale;
     HIPCHK(ctx, hipMemcpyAsync(T.center[T.cur], c.data(), sizeof(float) * (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(T.scale[T.cur], s.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(T.valid(), v.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -2933,7 +3039,7 @@ int hp3d_track_seed(hp3d_ctx* ctx, int B, int H, int W, const float* center, con
     HIPCHK(ctx, hipMemsetAsync(T.lost, 0, sizeof(int) * (size_t)B, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < B; ++b) T.h_lost[b] = 0;
-    T.valid = true; T.B = B; T.H = H; T.W = W; T.since = 0;
+    T.valid = true; T.B = B; T.H = H; T.W = W; T.f = ctx->detect_scale; T.since = 0;
     return 0;
 }
 
@@ -3001,6 +3107,67 @@ int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H
     crop_and_resize_u8_launch(d_x, B, H, W, d_c, d_s, crop_size, d_o, ctx->stream);
     ++ctx->crop_u8_launches;
     HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+// ---- detection on a reduced frame: the per-op forms -------------------------------------------------------
+static int downscale_impl(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int f, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if ((!image && !image_u8) || !out || B < 1 || H < 1 || W < 1 || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const size_t ni = (size_t)B * H * W * 3, no = (size_t)B * Hd * Wd * 3;
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    if (image_u8) {
+        unsigned char* d_x = S.upload(image_u8, ni); NN(ctx, d_x);
+        downscale_u8_launch(d_x, B, H, W, f, d_o, ctx->stream);
+    } else {
+        float* d_x = S.upload(image, ni); NN(ctx, d_x);
+        downscale_launch(d_x, B, H, W, f, d_o, ctx->stream);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_downscale(hp3d_ctx* ctx, const float* image, int B, int H, int W, int f, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    return downscale_impl(ctx, image, nullptr, B, H, W, f, out);
+}
+int hp3d_downscale_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, int f, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    return downscale_impl(ctx, nullptr, image_u8, B, H, W, f, out);
+}
+
+int hp3d_boxes_to_frame(hp3d_ctx* ctx, int n, int f, const float* center_d, const float* crop_size_d, float* center, float* crop_size,
+                        float* scale) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!center_d || !crop_size_d || !center || !crop_size || !scale || n < 1 || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    float* d_c = S.upload(center_d, (size_t)n * 2); NN(ctx, d_c);
+    float* d_cs = S.upload(crop_size_d, (size_t)n); NN(ctx, d_cs);
+    float* d_s = S.alloc<float>(n); NN(ctx, d_s);
+    box_to_frame_launch(d_c, d_cs, n, f, d_c, d_cs, d_s, ctx->stream);          // in place, as the step runs it
+    HIPCHK(ctx, hipMemcpyAsync(center, d_c, sizeof(float) * (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(crop_size, d_cs, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(scale, d_s, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const float* scale, float* center_d, float* scale_d) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!center || !scale || !center_d || !scale_d || n < 1 || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    float* d_c = S.upload(center, (size_t)n * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)n); NN(ctx, d_s);
+    float* d_cd = S.alloc<float>((size_t)n * 2); NN(ctx, d_cd);
+    float* d_sd = S.alloc<float>(n); NN(ctx, d_sd);
+    box_to_detect_launch(d_c, d_s, n, f, d_cd, d_sd, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(center_d, d_cd, sizeof(float) * (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(scale_d, d_sd, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
 
@@ -3371,6 +3538,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"track_hands_detect_steps", &Counters::track_hands_detect_steps, false},
         {"track_hands_tracked_steps", &Counters::track_hands_tracked_steps, false},
         {"crop_u8_launches", &Counters::crop_u8_launches, false},
+        {"detect_scale_steps", &Counters::detect_scale_steps, false},
     };
     const std::string k(name);
     for (const auto& c : table)
@@ -3379,6 +3547,10 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
     if (k == "emu_soff_overreads") { *value = (long)hp3d_emu_soff_overreads; return 0; }     // interpreter only: 16-byte loads that left their buffer through the scalar offset
 #endif
     if (k == "comm_ranks") { *value = comm_ranks(ctx); return 0; }
+    if (k == "arena_bytes") {          // the frame-sized buffers of this context: the two activation buffers, image, staging, score map, mask, fg, det
+        *value = (long long)(4 * (2 * ctx->act_floats + ctx->image_floats + ctx->stage_floats + ctx->large_floats + ctx->mask_floats + ctx->large_floats / 2) + ctx->det_bytes);
+        return 0;
+    }
     HP3D_FAIL(ctx, HP3D_ERR_ARG, "unknown counter %s", name);
 }
 int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n) {

@@ -1602,6 +1602,89 @@ void track_select_kernel(const int* lost_prev, const float* det_center, const fl
     }
 }
 
+// ---- detection on a reduced frame (option "detect_scale" = f) -------------------------------------------------------
+// The detection frame: pixel (y, x, c) of the [Hd, Wd] = [ceil(H / f), ceil(W / f)] output is the mean of the source window rows
+// [y f, min((y + 1) f, H)) x columns [x f, min((x + 1) f, W)) -- clipped, n = the real count.  float32 frames: the window added in
+// row-major order as a sequential float32 sum, then / float(n).  uint8 frames: the exact integer sum, then (float(sum) / float(n)) / 255
+// - 0.5 in preprocess_u8_kernel's order; the normalised full-size frame never exists.
+// One thread takes one output pixel with its 3 channels: a window row is f * 3 contiguous elements, the rows of neighbouring lanes lie
+// side by side (a wave reads 64 f * 3 contiguous elements of a frame row per load), the 3 floats written per lane likewise.  F > 0
+// (f = 2, 4, 8 with `wide`: frame base and row pitch multiples of ALIGN bytes): a full window row is ONE load of F * 3 elements at
+// the widest alignment the pixel size allows -- 8 / 16 / 16 bytes for float32, 2 / 4 / 8 bytes for uint8 (3 bytes per pixel: a window
+// row starts on a 16-byte boundary only every fourth window at f = 4) -- instead of F * 3 element loads.
+template <typename T> struct DownAcc { typedef float type; };
+template <> struct DownAcc<unsigned char> { typedef unsigned type; };
+__device__ __forceinline__ float downscale_finish(float sum, float n) { return sum / n; }
+__device__ __forceinline__ float downscale_finish(unsigned sum, float n) { return ((float)sum / n) / 255.0f - 0.5f; }
+template <typename T, int F>
+__device__ __forceinline__ void downscale_body(const T* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    typedef typename DownAcc<T>::type acc_t;
+    constexpr int NV = F > 0 ? F * 3 : 1;
+    constexpr int ROWB = NV * (int)sizeof(T);
+    constexpr int ALIGN = ROWB % 16 == 0 ? 16 : ROWB % 8 == 0 ? 8 : ROWB % 4 == 0 ? 4 : ROWB % 2 == 0 ? 2 : 1;
+    const long total = (long)B * Hd * Wd;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wd);
+        long r = i / Wd;
+        const int y = (int)(r % Hd);
+        const int b = (int)(r / Hd);
+        const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
+        acc_t s0 = 0, s1 = 0, s2 = 0;
+        const T* p = img + (((size_t)b * H + y0) * W + x0) * 3;
+        for (int yy = y0; yy < y1; ++yy, p += (size_t)W * 3) {
+            if (F > 0 && wide && nx == F) {
+                T v[NV];
+                __builtin_memcpy(v, __builtin_assume_aligned(p, ALIGN), sizeof(v));
+#pragma unroll
+                for (int k = 0; k < NV; k += 3) { s0 += v[k]; s1 += v[k + 1]; s2 += v[k + 2]; }
+            } else {
+                for (int k = 0; k < nx * 3; k += 3) { s0 += p[k]; s1 += p[k + 1]; s2 += p[k + 2]; }
+            }
+        }
+        const float n = (float)((y1 - y0) * nx);
+        float* o = out + (size_t)i * 3;
+        o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
+    }
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_kernel(const float* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_body<float, F>(img, B, H, W, f, Hd, Wd, wide, out);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_u8_kernel(const unsigned char* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_body<unsigned char, F>(img, B, H, W, f, Hd, Wd, wide, out);
+}
+
+// A detection-frame box (centre_d, crop_size_d) in frame coordinates: centre = centre_d * f + (f - 1) / 2 (the centre of detection pixel
+// p covers frame pixels p f ... p f + f - 1), crop_size = crop_size_d * f, scale from it as mask_grow_epilogue derives it (NumPy's NaN
+// rules: oracle.general.scale_from_crop_size).  Element by element: may run in place.
+HP3D_KERNEL(256)
+void box_to_frame_kernel(const float* center_d, const float* crop_size_d, int n, float ff, float off, float* center, float* crop_size,
+                         float* scale) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float cy = center_d[i * 2] * ff + off, cx = center_d[i * 2 + 1] * ff + off;
+        const float sz = crop_size_d[i] * ff;
+        center[i * 2] = cy; center[i * 2 + 1] = cx;
+        if (crop_size) crop_size[i] = sz;
+        const float best = sz * 1.25f;
+        scale[i] = np_minimum(np_maximum(256.0f / best, 0.25f), 5.0f);
+    }
+}
+
+// The other direction for the slots a multi-hand detect step keeps: the claim rule (mask_claims) compares them with objects of the
+// detection frame.  centre_d = (centre - (f - 1) / 2) / f, scale_d = scale * f (half = 128 / scale_d: the window's half side in
+// detection pixels).
+HP3D_KERNEL(256)
+void box_to_detect_kernel(const float* center, const float* scale, int n, float ff, float off, float* center_d, float* scale_d) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        center_d[i * 2] = (center[i * 2] - off) / ff;
+        center_d[i * 2 + 1] = (center[i * 2 + 1] - off) / ff;
+        scale_d[i] = scale[i] * ff;
+    }
+}
+
 inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
     long g = (total + block - 1) / block;
     if (g < 1) g = 1;
@@ -1815,6 +1898,33 @@ void track_hands_select_launch(const int* keep, const float* det_center, const f
                                int n, float* box_center, float* box_scale, int* valid, int* detected, int* area, hipStream_t s) {
     HP3D_LAUNCH(track_hands_select_kernel, dim3(grid_for(n)), dim3(256), 0, s, keep, det_center, det_scale, det_valid, det_area, n,
                 box_center, box_scale, valid, detected, area);
+}
+// T = float | unsigned char; the wide form where f is 2, 4 or 8 and every window row starts on the load's alignment
+template <typename T, class K0, class K2, class K4, class K8>
+static void downscale_dispatch(K0 k0, K2 k2, K4 k4, K8 k8, const T* img, int B, int H, int W, int f, float* out, hipStream_t s) {
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const int rowb = f * 3 * (int)sizeof(T);
+    const int align = rowb % 16 == 0 ? 16 : rowb % 8 == 0 ? 8 : rowb % 4 == 0 ? 4 : rowb % 2 == 0 ? 2 : 1;
+    const int wide = ((uintptr_t)img % align == 0 && ((size_t)W * 3 * sizeof(T)) % align == 0) ? 1 : 0;
+    const dim3 grid(grid_for((long)B * Hd * Wd)), block(256);
+    if (f == 2) HP3D_LAUNCH(k2, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
+    else if (f == 4) HP3D_LAUNCH(k4, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
+    else if (f == 8) HP3D_LAUNCH(k8, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
+    else HP3D_LAUNCH(k0, grid, block, 0, s, img, B, H, W, f, Hd, Wd, 0, out);
+}
+void downscale_launch(const float* img, int B, int H, int W, int f, float* out, hipStream_t s) {
+    downscale_dispatch(downscale_kernel<0>, downscale_kernel<2>, downscale_kernel<4>, downscale_kernel<8>, img, B, H, W, f, out, s);
+}
+void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, float* out, hipStream_t s) {
+    downscale_dispatch(downscale_u8_kernel<0>, downscale_u8_kernel<2>, downscale_u8_kernel<4>, downscale_u8_kernel<8>, img, B, H, W, f, out, s);
+}
+void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
+                         hipStream_t s) {
+    HP3D_LAUNCH(box_to_frame_kernel, dim3(grid_for(n)), dim3(256), 0, s, center_d, crop_size_d, n, (float)f, (float)(f - 1) / 2.0f, center,
+                crop_size, scale);
+}
+void box_to_detect_launch(const float* center, const float* scale, int n, int f, float* center_d, float* scale_d, hipStream_t s) {
+    HP3D_LAUNCH(box_to_detect_kernel, dim3(grid_for(n)), dim3(256), 0, s, center, scale, n, (float)f, (float)(f - 1) / 2.0f, center_d, scale_d);
 }
 void argmax2d_launch(const float* x, int B, int H, int W, int C, int cs, int* out_rc, hipStream_t s) {
     HP3D_LAUNCH(argmax2d_kernel, dim3(C, B), dim3(256), 0, s, x, H, W, C, cs, out_rc);

@@ -467,6 +467,14 @@ void track_hands_box_launch(const double* kp_image, const float* sm, int cs, int
                             float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0, hipStream_t s);
 void track_hands_select_launch(const int* keep, const float* det_center, const float* det_scale, const int* det_valid, const int* det_area,
                                int n, float* box_center, float* box_scale, int* valid, int* detected, int* area, hipStream_t s);
+// detection on a reduced frame (option "detect_scale" = f in 2 ... 8): the [B,ceil(H/f),ceil(W/f),3] area mean of a float32
+// frame / of a uint8 frame normalised as preprocess_u8 does; a detection-frame box (centre, crop size) in frame coordinates with its
+// scale (in place allowed; crop_size may be null); a kept slot's frame box in detection-frame coordinates
+void downscale_launch(const float* img, int B, int H, int W, int f, float* out, hipStream_t s);
+void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, float* out, hipStream_t s);
+void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
+                         hipStream_t s);
+void box_to_detect_launch(const float* center, const float* scale, int n, int f, float* center_d, float* scale_d, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

@@ -150,7 +150,11 @@ class ColorHandPose3DNetwork(object):
             o = self.engine.infer_hands(image, hand_side, max_hands)
         return (o['scoremap'], o['crop'], o['scale'], o['center'], o['kpmap'], o['coord3d'], o['valid'], o['area'], o['kp_hw'])
 
-    def track(self, image, hand_side):
+    def _detect_scale(self, detect_scale):
+        if detect_scale is not None:
+            self.engine.set_option('detect_scale', str(int(detect_scale)))
+
+    def track(self, image, hand_side, detect_scale=None):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
             HandSegNet as inference() does; every other call crops with the box the dataset readers' hand_crop rule
@@ -158,7 +162,10 @@ class ColorHandPose3DNetwork(object):
             `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3] (tracked steps then crop straight from the uint8 frame).
             Returns what inference_keypoints() returns -- keypoint_coord3d, keypoint_hw, keypoint_hw_crop, scale_crop, center (the
             box this step used) -- plus confidence [B], lost [B] (1: the next step will detect again) and detected [B]
-            (1: this step's box came from HandSegNet). """
+            (1: this step's box came from HandSegNet).
+            `detect_scale` = f in 1 ... 8 sets the engine option of that name, which stays set (None: as it is): a detect step finds the
+            hand on the frame's f x f area mean and crops from the frame itself; the outputs keep their shapes. """
+        self._detect_scale(detect_scale)
         step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
         o = step(image, hand_side)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],
@@ -168,7 +175,7 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
-    def track_hands(self, image, hand_side, max_hands):
+    def track_hands(self, image, hand_side, max_hands, detect_scale=None):
         """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
             keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
             A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
@@ -177,7 +184,8 @@ class ColorHandPose3DNetwork(object):
             `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3]; `hand_side` [B,K,2], one row per slot.
             Returns track()'s tuple with a K axis plus valid [B,K] (0: the slot holds no hand) and area [B,K] (pixels of the
             object where detected = 1).  The engine's `claimed` counters (objects a kept slot claimed on a detect step) are not in the
-            tuple: Engine.track_hands_step returns them. """
+            tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track(). """
+        self._detect_scale(detect_scale)
         step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step
         o = step(image, hand_side, max_hands)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],

@@ -153,6 +153,13 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            value depends on the trained weights: callers calibrate it on the confidence the steps return;
  *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image
  *                            (hp3d_track_hands_step*: that fills free slots only, kept slots are not re-boxed);
+ *          "detect_scale" = "1" (default) | "2" ... "8", an integer f: the DETECT steps of hp3d_track_step* / hp3d_track_hands_step* find the
+ *                            hand on the frame's f x f area mean ([ceil(H/f), ceil(W/f)], at least 16 x 16: HP3D_ERR_ARG before any launch
+ *                            otherwise) and crop from the frame itself; see "detection on a reduced frame" below.  "1": detect on the
+ *                            frame, every call enqueues what it did without the option.  Tracked steps are the same at every f.
+ *                            hp3d_infer_full*, hp3d_infer_2d* and hp3d_infer_hands* IGNORE the option (their score-map and mask outputs
+ *                            have the frame's size).  A change between two steps counts as a change of shape: the next step detects.
+ *                            The default and which f still finds a hand are policy, not measurement;
  *          "hands_min_area" = "0" (default: off) | N: hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer than N pixels
  *                            instead of reporting them as hands.  A useful value depends on the trained weights: callers calibrate it on
  *                            the `area` every call returns;
@@ -326,6 +333,31 @@ int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw
 int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, const float* center,
                             const float* scale, int crop_size, float* out);
 
+/* ---- detection on a reduced frame (option "detect_scale" = f > 1) ----------------
+ * A detect step of hp3d_track_step* / hp3d_track_hands_step* then runs, all in float32 op by op:
+ *  1. the detection frame [Hd, Wd] = [ceil(H/f), ceil(W/f)]: pixel (y, x, c) = the mean of the frame's rows [y f, min((y+1) f, H)) x
+ *     columns [x f, min((x+1) f, W)) (clipped windows, n = the real count).  float32 frames: the window added in row-major order as a
+ *     sequential float32 sum, / float(n).  uint8 frames (hp3d_*_step_u8): the exact integer sum, (float(sum) / float(n)) / 255 - 0.5;
+ *     the normalised full-size frame is never built (no preprocess_u8 launch);
+ *  2. HandSegNet, the soft-max and the mask growth at (Hd, Wd) exactly as on a frame of that size; `area`, option "hands_min_area" and
+ *     the growth cap are in detection-frame pixels;
+ *  3. every box the growth wrote (fall-back boxes and absent slots included) to the frame: centre = centre_d * f + (f - 1) / 2,
+ *     crop_size = crop_size_d * f, scale = clip(256 / (crop_size * 1.25), 0.25, 5);
+ *  4. (multi-hand) before the growth, the kept slots to the detection frame for the claim rule: centre_d = (centre - (f - 1) / 2) / f,
+ *     scale_d = scale * f;
+ *  5. the per-image / per-slot choice, the crop -- from the FULL frame (hp3d_*_step_u8: straight from the uint8 frame, counted in
+ *     "crop_u8_launches") -- and everything behind it in frame coordinates as without the option.
+ * The activation arena and the micro-batch limit follow (Hd, Wd).  Profile rows "downscale" / "downscale_u8", "box_to_frame",
+ * "box_to_detect"; counter "detect_scale_steps".  The per-op forms (host pointers, f in 1 ... 8):
+ * hp3d_downscale / hp3d_downscale_u8  image [B,H,W,3] float32 / uint8 -> out [B,ceil(H/f),ceil(W/f),3] (rule 1)
+ * hp3d_boxes_to_frame   center_d [n,2], crop_size_d [n] -> center [n,2], crop_size [n], scale [n] (rule 3)
+ * hp3d_boxes_to_detect  center [n,2], scale [n] -> center_d [n,2], scale_d [n] (rule 4)                                          */
+int hp3d_downscale(hp3d_ctx* ctx, const float* image, int B, int H, int W, int f, float* out);
+int hp3d_downscale_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int W, int f, float* out);
+int hp3d_boxes_to_frame(hp3d_ctx* ctx, int n, int f, const float* center_d, const float* crop_size_d, float* center, float* crop_size,
+                        float* scale);
+int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const float* scale, float* center_d, float* scale_d);
+
 /* ---- several hands per frame --------------------------------------------------
  * The whole-path calls above keep ONE object of HandSegNet's detection map per image: the one that grows from the arg-max of the
  * foreground score (single_obj_scoremap, utils/general.py:233-268).  These calls return up to K of them, 1 <= K <= HP3D_MAX_HANDS, from
@@ -485,6 +517,8 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "track_detect_steps" / "track_tracked_steps" = hp3d_track_step* calls that ran HandSegNet / that cropped from the previous step's keypoints;
  * "track_hands_detect_steps" / "track_hands_tracked_steps" = the same for hp3d_track_hands_step*;
  * "crop_u8_launches" = crops taken straight from a uint8 frame (tracked steps of hp3d_track_step_u8 / hp3d_track_hands_step_u8, one per chunk; hp3d_crop_and_resize_u8);
+ * "detect_scale_steps" = detect steps of hp3d_track_step* / hp3d_track_hands_step* that ran at option "detect_scale" > 1; "arena_bytes" = bytes of
+ * the context's frame-sized device buffers (the two activation buffers, image, staging, score map, mask, foreground, detection map);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
