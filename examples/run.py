@@ -16,6 +16,8 @@ if __name__ == '__main__':
     ap = parser(__doc__)
     ap.add_argument('images', nargs='*')
     ap.add_argument('--hands', type=int, default=1, help="up to K hands per image (1 ... 4; default 1: the reference's output)")
+    ap.add_argument('--compact', action='store_true',
+                    help='with --hands K: run PoseNet2D and the lifting stage on the slots that hold a hand only (DESIGN.md 4.15)')
     a = ap.parse_args()
     from hand3d_amd import synth
     from hand3d_amd.nets.ColorHandPose3DNetwork import ColorHandPose3DNetwork
@@ -35,7 +37,7 @@ if __name__ == '__main__':
         image_v = np.expand_dims((image_raw.astype('float') / 255.0) - 0.5, 0)                       # run.py:59
         if a.hands > 1:          # every slot as a left hand, like run.py:40
             _, _, scale_k, center_k, _, coord3d_k, valid, area, kp_hw = \
-                net.inference_hands(image_v, np.tile(hand_side_v, (1, a.hands, 1)), a.hands)
+                net.inference_hands(image_v, np.tile(hand_side_v, (1, a.hands, 1)), a.hands, compact=a.compact)
             for k in range(a.hands):
                 if valid[0, k]:
                     print(json.dumps({'image': i, 'hand': k, 'area': int(area[0, k]), 'center': center_k[0, k].tolist(),

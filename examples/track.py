@@ -26,6 +26,8 @@ if __name__ == '__main__':
                     help='follow up to K hands per frame, each in its own slot (0: the single-hand tracker)')
     ap.add_argument('--detect-scale', type=int, default=1, metavar='F', choices=range(1, 9),
                     help='detect steps find the hand on the F x F area mean of the frame and crop from the frame itself (1: detect on the frame)')
+    ap.add_argument('--compact', action='store_true',
+                    help='with --hands K: slots without a hand cost nothing behind their box and report zeros (DESIGN.md 4.15)')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -70,7 +72,7 @@ if __name__ == '__main__':
             image_v = frame[None].astype(np.float32)
         ndet = net.engine.counter('track_hands_detect_steps')
         if a.hands:
-            coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands)
+            coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands, compact=a.compact)
             print(json.dumps({'frame': i, 'step': 'detect' if net.engine.counter('track_hands_detect_steps') > ndet else 'tracked',
                               'slots': [{'slot': k, 'valid': int(valid[0, k]), 'detected': int(detected[0, k]), 'area': int(area[0, k]),
                                          'center': center[0, k].tolist(), 'scale': float(scale[0, k]),

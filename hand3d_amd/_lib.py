@@ -77,6 +77,9 @@ _SIGNATURES = {
     'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
     'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
     'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'hp3d_crop_and_resize_idx': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_slot_scatter': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_boxes_to_frame': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 5),
@@ -572,6 +575,32 @@ class Engine(object):
         return out
 
     # -- detection on a reduced frame (include/hp3d.h): the per-op forms ----------------
+    def crop_and_resize_idx(self, image, center, scale, idx, K, crop_size=256):
+        """Crop i = box idx[i] of center [B*K,2] / scale [B*K], cut from image idx[i] // K (option "hands_compact", DESIGN.md 4.15).
+        image [B,H,W,3] float32 or uint8 (then normalised tap by tap as preprocess_u8 does) -> [m,crop_size,crop_size,3]."""
+        u8 = np.asarray(image).dtype == np.uint8
+        image = np.ascontiguousarray(image, dtype=np.uint8 if u8 else np.float32)
+        B, H, W, _ = image.shape
+        center, scale = _f32(center), _f32(scale)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        out = np.empty((idx.size, crop_size, crop_size, 3), np.float32)
+        self._chk(self.lib.hp3d_crop_and_resize_idx(self.h, None if u8 else _ptr(image), _ptr(image) if u8 else None, B, H, W, int(K),
+                                                    _ptr(center), _ptr(scale), _ptr(idx), int(idx.size), int(crop_size), _ptr(out)))
+        return out
+
+    def slot_scatter(self, dense, pos, skew_words=0, sentinel=-7.0):
+        """dense [m,...] (any 4-byte dtype) -> [ns,...] with out[s] = dense[pos[s]], 0 where pos[s] = -1 (option "hands_compact").
+        Returns (out, tail): tail = the 4 words behind the last slot, which were `sentinel` before the launch."""
+        dense = np.ascontiguousarray(dense)
+        assert dense.dtype.itemsize == 4
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        m, ns = dense.shape[0], pos.size
+        words = int(np.prod(dense.shape[1:]))
+        buf = np.full(ns * words + 4, sentinel, np.float32)
+        self._chk(self.lib.hp3d_slot_scatter(self.h, _ptr(dense.view(np.float32)) if m else None, _ptr(pos), ns, m, words, int(skew_words),
+                                             _ptr(buf)))
+        return buf[:ns * words].view(dense.dtype).reshape((ns,) + dense.shape[1:]), buf[ns * words:]
+
     def downscale(self, image, f):
         """The detection frame of float32 frames [B,H,W,3]: the f x f area mean [B,ceil(H/f),ceil(W/f),3] (clipped windows)."""
         image = _f32(image)

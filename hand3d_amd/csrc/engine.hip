@@ -282,6 +282,8 @@ struct Options {
     int hands_min_area = 0;         // option "hands_min_area": hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer pixels (0: off)
     int detect_scale = 1;           // option "detect_scale": the detect steps of hp3d_track_step* / hp3d_track_hands_step* find the hand on the frame's
                                     // f x f area mean and crop from the frame itself (1: detect on the frame)
+    int hands_compact = 0;          // option "hands_compact": hp3d_infer_hands* / hp3d_track_hands_step* run the back half on the slots that hold a
+                                    // hand only; 0: every slot runs, absent ones on their fall-back crop
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -311,6 +313,21 @@ struct Counters {
     long crop_u8_launches = 0;                      // crops taken straight from a uint8 frame (crop_and_resize_u8_kernel)
     long track_hands_detect_steps = 0, track_hands_tracked_steps = 0;      // hp3d_track_hands_step*: as track_*_steps
     long detect_scale_steps = 0;                    // detect steps of either tracker that ran at detect_scale > 1
+    long hands_compact_slots_run = 0, hands_compact_slots_skipped = 0;     // option "hands_compact": slots whose back half ran / was skipped
+    long hands_compact_waits = 0;                   // ... and the stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*)
+};
+
+// Option "hands_compact" (DESIGN.md 4.15).  h_map: two page-locked buffers used in turn, idx [cap] | pos [cap] of one chunk; a buffer is
+// rewritten only after the event behind its last upload.  d_map: the same on the device (stream order protects it).
+struct CompactBufs {
+    int cap = 0;                        // slots the buffers hold
+    int* h_map[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    int turn = 0;
+    int* h_valid = nullptr;             // page-locked: a chunk's valid flags (detect steps, hp3d_infer_hands*)
+    int* d_map = nullptr;
+    float *d_hs = nullptr, *d_center = nullptr, *d_scale = nullptr;      // hand_side / centre / scale of the slots that run, dense
 };
 
 // What a context knows about the hands it follows (hp3d_track_*): the boxes for the next step, on the device, and the host's copy of the
@@ -419,6 +436,7 @@ struct hp3d_ctx : Options, Counters {
     size_t mg_words = 0;
     TrackState track;
     TrackHandsState track_hands;
+    CompactBufs compact;
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -1945,9 +1963,196 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     return 0;
 }
 
+// ---- compaction of absent hand slots (option "hands_compact") ---------------------------------------------------------
+int ensure_compact(hp3d_ctx* ctx, int ns) {
+    CompactBufs& Q = ctx->compact;
+    if (ns <= Q.cap) return 0;
+    for (int t = 0; t < 2; ++t)
+        if (Q.busy[t]) { HIPCHK(ctx, hipEventSynchronize(Q.ev[t])); Q.busy[t] = false; }
+    CHK(dev_realloc(ctx, &Q.d_map, (size_t)ns * 2));
+    CHK(dev_realloc(ctx, &Q.d_hs, (size_t)ns * 2));
+    CHK(dev_realloc(ctx, &Q.d_center, (size_t)ns * 2));
+    CHK(dev_realloc(ctx, &Q.d_scale, (size_t)ns));
+    int** hp[] = {&Q.h_map[0], &Q.h_map[1], &Q.h_valid};
+    for (int** h : hp) {
+#ifdef HP3D_EMU
+        free(*h);
+        *h = (int*)malloc(sizeof(int) * (size_t)ns * 2);
+#else
+        if (*h) HIPCHK(ctx, hipHostFree(*h));
+        *h = nullptr;
+        HIPCHK(ctx, hipHostMalloc((void**)h, sizeof(int) * (size_t)ns * 2, hipHostMallocDefault));
+#endif
+        if (!*h) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "hands_compact: host allocation failed");
+    }
+    for (int t = 0; t < 2; ++t)
+        if (!Q.ev[t]) {
+#ifdef HP3D_EMU
+            HIPCHK(ctx, hipEventCreate(&Q.ev[t]));
+#else
+            HIPCHK(ctx, hipEventCreateWithFlags(&Q.ev[t], hipEventDisableTiming));
+#endif
+        }
+    Q.cap = ns;
+    return 0;
+}
+
+void compact_free(hp3d_ctx* ctx) {
+    CompactBufs& Q = ctx->compact;
+    for (void* p : {(void*)Q.d_map, (void*)Q.d_hs, (void*)Q.d_center, (void*)Q.d_scale})
+        if (p) hipFree(p);
+    for (int* h : {Q.h_map[0], Q.h_map[1], Q.h_valid}) {
+#ifdef HP3D_EMU
+        free(h);
+#else
+        if (h) hipHostFree(h);
+#endif
+    }
+    for (int t = 0; t < 2; ++t)
+        if (Q.ev[t]) hipEventDestroy(Q.ev[t]);
+    Q = CompactBufs();
+}
+
+// A chunk's valid flags on the host, where only the device has them (detect steps, hp3d_infer_hands*): one small copy and one stream
+// synchronise, behind a HandSegNet pass (the only wait that "hands_compact_waits" counts).  Tracked steps never come here: the
+// state's flags are on the host already.
+int compact_wait_flags(hp3d_ctx* ctx, const int* d_valid, int ns, const int** h_valid) {
+    CHK(ensure_compact(ctx, ns));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->compact.h_valid, d_valid, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ++ctx->hands_compact_waits;
+    *h_valid = ctx->compact.h_valid;
+    return 0;
+}
+
+// One chunk of a multi-hand call behind its boxes: what the compacted back half needs to know.
+struct CompactChunk {
+    int nb, K, H, W;
+    const int* h_valid;                  // host: the chunk's nb * K flags
+    const float* d_img;                  // the chunk's frames, float32 ...
+    const unsigned char* d_u8;           // ... or, when not null, uint8: the crop comes straight from them
+    const float *center, *scale, *hand_side;      // device, slot layout
+    float *image_crop, *kp_scoremap, *coord3d;    // the chunk's outputs, slot layout (null: skipped); device pointers when dev
+    int32_t* kp_crop;
+    double* kp_image;
+    bool dev;
+    bool want_kp;                        // run kp_detect (hp3d_infer_hands*: only when asked for; the tracker: always)
+    // the multi-hand tracker's box step (null: hp3d_infer_hands*): the chunk's slice of the state
+    const std::function<void(const double* kp_image_dense, const int* pos)>* box = nullptr;
+};
+
+// The back half at batch m = the chunk's valid slots.  *compacted = false (m = ns: no absent slot): nothing is enqueued, the caller
+// takes the uncompacted path.  Otherwise: idx / pos upload, gather, indexed crop, PoseNet2D / lifting / up-sampling / kp_detect at batch
+// m (nothing of it when m = 0), the tracker's box step, and the scatter into the caller's buffers (dev) or into a staging area in bufA
+// -- free once the lifting stage is enqueued -- that is then copied out.  image_crop, kp_scoremap, coord3d, kp_crop and kp_image of
+// the chunk are complete behind it; the caller copies out the rest as without the option.
+int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted) {
+    const int ns = c.nb * c.K;
+    int m = 0;
+    for (int s = 0; s < ns; ++s) m += c.h_valid[s] != 0;
+    ctx->hands_compact_slots_run += m;
+    ctx->hands_compact_slots_skipped += ns - m;
+    *compacted = m < ns;
+    if (m == ns) return 0;
+    CHK(ensure_compact(ctx, ns));
+    CompactBufs& Q = ctx->compact;
+    const int t = Q.turn;
+    Q.turn ^= 1;
+    // (an event wait on the upload of two compacted chunks ago, not a stream synchronise and not counted: it can hold the host only in
+    //  a call of three or more compacted chunks that runs ahead of the device by two of them; ensure_compact waits likewise when the
+    //  slot count grows)
+    if (Q.busy[t]) { HIPCHK(ctx, hipEventSynchronize(Q.ev[t])); Q.busy[t] = false; }
+    int* idx = Q.h_map[t];
+    int* pos = idx + ns;
+    for (int s = 0, i = 0; s < ns; ++s) {
+        pos[s] = c.h_valid[s] ? i : -1;
+        if (c.h_valid[s]) idx[i++] = s;
+    }
+    for (int i = m; i < ns; ++i) idx[i] = 0;
+    HIPCHK(ctx, hipMemcpyAsync(Q.d_map, idx, sizeof(int) * (size_t)ns * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(Q.ev[t], ctx->stream));
+    Q.busy[t] = true;
+    const int* d_idx = Q.d_map;
+    const int* d_pos = Q.d_map + ns;
+    if (m > 0) {
+        {
+            ProfScope ps(ctx, "slot_gather", "slot_gather", 0.0, 24.0 * m);
+            slot_gather_launch(d_idx, m, c.hand_side, c.center, c.scale, Q.d_hs, Q.d_center, Q.d_scale, ctx->stream);
+        }
+        if (c.d_u8) {
+            ProfScope ps(ctx, "crop_and_resize_idx_u8", "crop_and_resize_idx_u8", 0.0, 1.0 * c.nb * c.H * c.W * 3 + 4.0 * m * 256 * 256 * 3);
+            crop_and_resize_idx_u8_launch(c.d_u8, m, c.H, c.W, c.center, c.scale, d_idx, c.K, 256, ctx->d_crop, ctx->stream);
+            ++ctx->crop_u8_launches;
+        } else {
+            ProfScope ps(ctx, "crop_and_resize_idx", "crop_and_resize_idx", 0.0, 4.0 * ((double)c.nb * c.H * c.W * 3 + (double)m * 256 * 256 * 3));
+            crop_and_resize_idx_launch(c.d_img, m, c.H, c.W, 3, c.center, c.scale, d_idx, c.K, 256, ctx->d_crop, ctx->stream);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        CHK(run_posenet(ctx, ctx->d_crop, m, 256, 256, true));
+        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
+            if (c.kp_scoremap) {
+                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * m * (32 * 32 * 21 + 256 * 256 * 21));
+                resize_bilinear_launch(ctx->d_sm[2], m, 32, 32, 21, 32, 256, 256, ctx->d_kpmap, st);
+            }
+            return 0;
+        };
+        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
+            if (c.want_kp) CHK(run_kp_detect(ctx, m, nullptr, nullptr, true, Q.d_scale, Q.d_center));
+            if (c.box) (*c.box)(ctx->d_kpimg, d_pos);
+            return 0;
+        };
+        CHK(run_pose3d(ctx, ctx->d_sm[2], Q.d_hs, m, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+    } else if (c.box) {
+        (*c.box)(ctx->d_kpimg, d_pos);
+    }
+    // dense -> slot layout.  Host forms: a staging area in bufA (ns * 24 * 65536 floats and the small arrays; bufA holds 64 * 65536 per slot)
+    float* st = ctx->bufA;
+    auto stage = [&](size_t words) { float* p = st; st += (words + 3) & ~(size_t)3; return p; };
+    float* s_crop = stage((size_t)ns * 256 * 256 * 3);
+    float* s_kpmap = stage((size_t)ns * 256 * 256 * 21);
+    float* s_coord = stage((size_t)ns * 63);
+    float* s_kpcrop = stage((size_t)ns * 42);
+    float* s_kpimg = stage((size_t)ns * 84);
+    ScatterPlan plan;
+    plan.add(ctx->d_crop, c.image_crop ? (c.dev ? c.image_crop : s_crop) : nullptr, 256 * 256 * 3);
+    plan.add(ctx->d_kpmap, c.kp_scoremap ? (c.dev ? c.kp_scoremap : s_kpmap) : nullptr, 256 * 256 * 21);
+    plan.add(ctx->d_coord, c.coord3d ? (c.dev ? c.coord3d : s_coord) : nullptr, 63);
+    plan.add(ctx->d_kpcrop, c.kp_crop ? (c.dev ? (float*)c.kp_crop : s_kpcrop) : nullptr, 42);
+    plan.add(ctx->d_kpimg, c.kp_image ? (c.dev ? (float*)c.kp_image : s_kpimg) : nullptr, 84);
+    if (plan.n > 0) {
+        ProfScope ps(ctx, "slot_scatter", "slot_scatter", 0.0, plan.bytes(ns, m));
+        slot_scatter_launch(plan, d_pos, ns, ctx->stream);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (!c.dev) {
+        CHK(copy_out(ctx, c.image_crop, s_crop, (size_t)ns * 256 * 256 * 3, false));
+        CHK(copy_out(ctx, c.kp_scoremap, s_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        CHK(copy_out(ctx, c.coord3d, s_coord, (size_t)ns * 63, false));
+        CHK(copy_out(ctx, (float*)c.kp_crop, s_kpcrop, (size_t)ns * 42, false));           // (int32 / float64: four bytes a word, as copy_out counts)
+        CHK(copy_out(ctx, (float*)c.kp_image, s_kpimg, (size_t)ns * 84, false));
+    }
+    return 0;
+}
+
+// The crop of every slot of a chunk, for a compacted call's chunk without an absent slot: the launch and the profile row of the
+// uncompacted path.
+int crop_all_slots(hp3d_ctx* ctx, const CompactChunk& c) {
+    const int ns = c.nb * c.K;
+    if (c.d_u8) {
+        ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * c.nb * c.H * c.W * 3 + 4.0 * ns * 256 * 256 * 3);
+        crop_and_resize_u8_launch(c.d_u8, ns, c.H, c.W, c.center, c.scale, 256, ctx->d_crop, ctx->stream, c.K);
+        ++ctx->crop_u8_launches;
+    } else {
+        ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * c.nb * (c.H * c.W * 3 + c.K * 256 * 256 * 3));
+        crop_and_resize_launch(c.d_img, ns, c.H, c.W, 3, c.center, c.scale, 256, ctx->d_crop, ctx->stream, c.K);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 // Up to K hands per frame: HandSegNet, the soft-max and ONE multi-hand mask growth per chunk of frames, then the back
 // half of infer_full_impl -- PoseNet2D, the lifting towers with the heat-map up-sampling and the keypoint detection beside them -- at
-// batch nb * K with per-slot centre / scale / hand_side.  No compaction: absent slots run on their fall-back crop, so a call has one
+// batch nb * K with per-slot centre / scale / hand_side.  No compaction unless option "hands_compact" (DESIGN.md 4.15): absent slots run on their fall-back crop, so a call has one
 // kernel plan and no host wait.  A chunk holds at most micro_batch / K frames: no launch behind the crop sees more slots than a
 // single-hand call's chunk has images.  One stream, no graph replay.
 int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, int Hin, int Win,
@@ -1988,11 +2193,22 @@ int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
             d_img = ctx->d_image;
         }
         if (!dev) { CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false)); d_hs = ctx->d_hs; }
-        CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, true, K));
-        CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
         float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
         int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
         double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
+        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        bool compacted = false;          // option "hands_compact": the back half ran on the valid slots only and wrote its outputs
+        if (ctx->hands_compact) {
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, false, K));
+            CompactChunk cc{nb, K, H, W, nullptr, d_img, nullptr, ctx->d_center, ctx->d_scale, d_hs, off(image_crop, 256 * 256 * 3), kpmap_out,
+                            off(coord3d, 63), kpc_out, kpi_out, dev, kpc_out || kpi_out};
+            CHK(compact_wait_flags(ctx, ctx->d_valid, ns, &cc.h_valid));
+            CHK(run_compact_back_half(ctx, cc, &compacted));
+            if (!compacted) CHK(crop_all_slots(ctx, cc));
+        } else {
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, true, K));
+        }
+        if (!compacted) CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
         const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
             if (kpmap_out) {
                 ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
@@ -2004,14 +2220,13 @@ int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
             if (kpc_out || kpi_out) CHK(run_kp_detect(ctx, ns, kpc_out, kpi_out, dev));
             return 0;
         };
-        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
-        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        if (!compacted) CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
         CHK(copy_out(ctx, hand_scoremap ? hand_scoremap + (size_t)b0 * H * W * 2 : nullptr, ctx->d_large, (size_t)nb * H * W * 2, dev));
-        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
+        if (!compacted) CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
         CHK(copy_out(ctx, off(scale_crop, 1), ctx->d_scale, (size_t)ns, dev));
         CHK(copy_out(ctx, off(center, 2), ctx->d_center, (size_t)ns * 2, dev));
-        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
-        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
+        if (!dev && !compacted) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        if (!compacted) CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
         CHK(copy_out(ctx, off(hand_mask, (size_t)H * W), ctx->d_mask, (size_t)ns * H * W, dev));
         CHK(copy_out(ctx, (float*)(valid ? valid + s0 : nullptr), (const float*)ctx->d_valid, (size_t)ns, dev));           // (int32: four bytes each, as copy_out counts)
         CHK(copy_out(ctx, (float*)(area ? area + s0 : nullptr), (const float*)ctx->d_area, (size_t)ns, dev));
@@ -2073,7 +2288,8 @@ void track_hands_free(hp3d_ctx* ctx) {
 // kept: an object one of them claims is dropped, the others fill the free slots in the order of discovery), the per-slot select, then
 // the crop.  TRACKED step: the K crops of a frame come from the state's boxes.  Behind the crop both are infer_hands_impl's back half
 // at batch nb * K plus the per-slot box rule.  Decided on the host, before anything is enqueued, from the valid | lost flags that travel
-// behind the previous step; the whole batch detects together; absent slots run on their fall-back crop (no compaction).
+// behind the previous step; the whole batch detects together; absent slots run on their fall-back crop (no compaction unless option
+// "hands_compact", DESIGN.md 4.15: run_compact_back_half).
 // (The frame of this function -- uint8 upload, profile save / restore, chunk loop, kp_up / kp_work, copy_out sequence -- repeats
 //  track_step_impl's, which this change leaves as it is: a fix to one of the two belongs in the other as well.)
 int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, const float* hand_side,
@@ -2123,6 +2339,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
     if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
     const int cur = T.cur, nxt = T.cur ^ 1;
+    const bool comp = ctx->hands_compact != 0;
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = std::min(mb, B - b0), ns = nb * K;
         const size_t s0 = (size_t)b0 * K;
@@ -2150,7 +2367,8 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
                 track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
                                           T.detected + s0, T.area + s0, ctx->stream);
             }
-            if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
+            if (comp) {              // (the crop follows the flags, below)
+            } else if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
                 ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
                 crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
                 ++ctx->crop_u8_launches;
@@ -2173,8 +2391,11 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
                 track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
                                           T.detected + s0, T.area + s0, ctx->stream);
             }
-            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
-            crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+            if (!comp) {
+                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
+                crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+            }
+        } else if (comp) {           // (a tracked step: the state's flags are on the host already)
         } else if (image_u8) {
             ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
             crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
@@ -2184,10 +2405,27 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
             crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
         }
         HIPCHK(ctx, hipGetLastError());
-        CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
         float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
         int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
         double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
+        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        bool compacted = false;          // option "hands_compact": the back half ran on the valid slots only and wrote its outputs
+        if (comp) {
+            // (a detect step at detect_scale = 1 has normalised a uint8 frame for HandSegNet and crops from that, as without the option)
+            const std::function<void(const double*, const int*)> box = [&](const double* kp_dense, const int* d_pos) {
+                ProfScope ps(ctx, "track_hands_box", "track_hands_box_pos", 0.0, 4.0 * ns * 32 * 32 * 21);
+                track_hands_box_pos_launch(kp_dense, ctx->d_sm[2], 32, ns, H, W, 256, ctx->track_margin, ctx->track_min_score,
+                                           ctx->track_use_min_score, d_pos, bc, bs, T.center[nxt] + s0 * 2, T.scale[nxt] + s0, T.conf + s0,
+                                           T.lost() + s0, T.keep + s0, detect ? nullptr : T.detected + s0, detect ? nullptr : T.area + s0,
+                                           detect ? nullptr : T.claimed + s0, ctx->stream);
+            };
+            CompactChunk cc{nb, K, H, W, T.h_flags + s0, d_img, image_u8 && (!detect || f > 1) ? d_u8 : nullptr, bc, bs, d_hs,
+                            off(image_crop, 256 * 256 * 3), kpmap_out, off(coord3d, 63), kpc_out, kpi_out, dev, true, &box};
+            if (detect) CHK(compact_wait_flags(ctx, T.valid() + s0, ns, &cc.h_valid));
+            CHK(run_compact_back_half(ctx, cc, &compacted));
+            if (!compacted) CHK(crop_all_slots(ctx, cc));
+        }
+        if (!compacted) CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
         const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
             if (kpmap_out) {
                 ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
@@ -2205,14 +2443,13 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
                                    detect ? nullptr : T.claimed + s0, ctx->stream);
             return 0;
         };
-        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
-        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        if (!compacted) CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
         auto offi = [&](int32_t* p) { return (float*)(p ? p + s0 : nullptr); };           // (int32: four bytes each, as copy_out counts)
-        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
+        if (!compacted) CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
         CHK(copy_out(ctx, off(scale_crop, 1), bs, (size_t)ns, dev));
         CHK(copy_out(ctx, off(center, 2), bc, (size_t)ns * 2, dev));
-        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
-        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
+        if (!dev && !compacted) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        if (!compacted) CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
         CHK(copy_out(ctx, off(confidence, 1), T.conf + s0, (size_t)ns, dev));
         CHK(copy_out(ctx, offi(lost), (const float*)(T.lost() + s0), (size_t)ns, dev));
         CHK(copy_out(ctx, offi(detected), (const float*)(T.detected + s0), (size_t)ns, dev));
@@ -2385,6 +2622,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
     if (ctx->d_mgscratch) hipFree(ctx->d_mgscratch);
     track_free(ctx);
     track_hands_free(ctx);
+    compact_free(ctx);
     if (ctx->d_u8) hipFree(ctx->d_u8);
     if (ctx->blob16) hipFree(ctx->blob16);
     if (ctx->d_concat16) hipFree(ctx->d_concat16);
@@ -2542,6 +2780,11 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
     if (k == "detect_scale") {
         if (v.size() != 1 || v[0] < '1' || v[0] > '8') HP3D_FAIL(ctx, HP3D_ERR_ARG, "detect_scale wants an integer in 1 ... 8, got %s", value);
         ctx->detect_scale = v[0] - '0';
+        return 0;
+    }
+    if (k == "hands_compact") {
+        if (v != "0" && v != "1") HP3D_FAIL(ctx, HP3D_ERR_ARG, "hands_compact wants 0 or 1, got %s", value);
+        ctx->hands_compact = v == "1";
         return 0;
     }
     if (k == "track_redetect") {
@@ -3110,6 +3353,56 @@ int hp3d_crop_and_resize_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H
     return finish_op(ctx);
 }
 
+// ---- compaction of absent hand slots: the per-op forms -----------------------------------------------------
+int hp3d_crop_and_resize_idx(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int K, const float* center,
+                             const float* scale, const int32_t* idx, int m, int crop_size, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if ((!image) == (!image_u8) || !center || !scale || !idx || !out || B < 1 || H < 2 || W < 2 || K < 1 || K > HP3D_MAX_HANDS || m < 0 ||
+        m > B * K || crop_size < 1)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    for (int i = 0; i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B * K) HP3D_FAIL(ctx, HP3D_ERR_ARG, "idx[%d] = %d is no slot of %d", i, (int)idx[i], B * K);
+    if (m == 0) return 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t no = (size_t)m * crop_size * crop_size * 3;
+    float* d_c = S.upload(center, (size_t)B * K * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)B * K); NN(ctx, d_s);
+    int32_t* d_i = S.upload(idx, (size_t)m); NN(ctx, d_i);
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    if (image_u8) {
+        unsigned char* d_x = S.upload(image_u8, (size_t)B * H * W * 3); NN(ctx, d_x);
+        crop_and_resize_idx_u8_launch(d_x, m, H, W, d_c, d_s, d_i, K, crop_size, d_o, ctx->stream);
+        ++ctx->crop_u8_launches;
+    } else {
+        float* d_x = S.upload(image, (size_t)B * H * W * 3); NN(ctx, d_x);
+        crop_and_resize_idx_launch(d_x, m, H, W, 3, d_c, d_s, d_i, K, crop_size, d_o, ctx->stream);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+int hp3d_slot_scatter(hp3d_ctx* ctx, const float* dense, const int32_t* pos, int ns, int m, int words, int skew_words, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!pos || !out || ns < 1 || m < 0 || m > ns || (m > 0 && !dense) || words < 1 || skew_words < 0 || skew_words > 3)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    for (int s = 0; s < ns; ++s)
+        if (pos[s] < -1 || pos[s] >= m) HP3D_FAIL(ctx, HP3D_ERR_ARG, "pos[%d] = %d is no dense index of %d", s, (int)pos[s], m);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t no = (size_t)ns * words + 4;
+    float* d_x = S.alloc<float>((size_t)std::max(m, 1) * words); NN(ctx, d_x);
+    if (m > 0) HIPCHK(ctx, hipMemcpyAsync(d_x, dense, sizeof(float) * (size_t)m * words, hipMemcpyHostToDevice, ctx->stream));
+    int32_t* d_p = S.upload(pos, (size_t)ns); NN(ctx, d_p);
+    float* d_o = S.alloc<float>(no + 4); NN(ctx, d_o);
+    HIPCHK(ctx, hipMemcpyAsync(d_o + skew_words, out, no * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    ScatterPlan plan;
+    plan.add(d_x, d_o + skew_words, (size_t)words);
+    slot_scatter_launch(plan, d_p, ns, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o + skew_words, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
 // ---- detection on a reduced frame: the per-op forms -------------------------------------------------------
 static int downscale_impl(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int f, float* out) {
     if (!ctx) return HP3D_ERR_ARG;
@@ -3539,6 +3832,9 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"track_hands_tracked_steps", &Counters::track_hands_tracked_steps, false},
         {"crop_u8_launches", &Counters::crop_u8_launches, false},
         {"detect_scale_steps", &Counters::detect_scale_steps, false},
+        {"hands_compact_slots_run", &Counters::hands_compact_slots_run, false},
+        {"hands_compact_slots_skipped", &Counters::hands_compact_slots_skipped, false},
+        {"hands_compact_waits", &Counters::hands_compact_waits, false},
     };
     const std::string k(name);
     for (const auto& c : table)

@@ -1685,6 +1685,127 @@ void box_to_detect_kernel(const float* center, const float* scale, int n, float 
     }
 }
 
+// ---- compaction of absent hand slots (option "hands_compact") --------------------------------------------------------
+// The back half of the multi-hand calls at batch m = the slots that hold a hand.  idx [m] = those slots' indices b K + j, ascending;
+// pos [ns] = a slot's dense index, -1 for an absent one.  The kernels stand beside the ones they restate (crop_and_resize_body,
+// track_hands_box_kernel), which compile to what they compiled to before.
+//
+// Dense crop i: box idx[i] of the slot-layout center / scale, cut from image idx[i] / K.  crop_and_resize_body's arithmetic op by op.
+template <class Tap>
+__device__ __forceinline__ void crop_and_resize_idx_body(const Tap tap, int m, int H, int W, int C, const float* center, const float* scale,
+                                                         const int* idx, int K, int crop, float* out) {
+    const long total = (long)m * crop * crop;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % crop);
+        long r = i / crop;
+        const int y = (int)(r % crop);
+        const int b = idx[(int)(r / crop)];
+        const float cs = (float)crop / scale[b];
+        const float half = floorf(cs / 2.0f);
+        float y1 = center[b * 2 + 0] - half, y2 = y1 + cs;
+        float x1 = center[b * 2 + 1] - half, x2 = x1 + cs;
+        y1 = y1 / (float)H; y2 = y2 / (float)H; x1 = x1 / (float)W; x2 = x2 / (float)W;
+        const float hs = (crop > 1) ? (y2 - y1) * (float)(H - 1) / (float)(crop - 1) : 0.f;
+        const float ws = (crop > 1) ? (x2 - x1) * (float)(W - 1) / (float)(crop - 1) : 0.f;
+        const float in_y = (crop > 1) ? y1 * (float)(H - 1) + (float)y * hs : 0.5f * (y1 + y2) * (float)(H - 1);
+        const float in_x = (crop > 1) ? x1 * (float)(W - 1) + (float)x * ws : 0.5f * (x1 + x2) * (float)(W - 1);
+        float* o = out + (size_t)i * C;
+        const bool ok = in_y >= 0.f && in_y <= (float)(H - 1) && in_x >= 0.f && in_x <= (float)(W - 1);
+        if (!ok) {
+            for (int c = 0; c < C; ++c) o[c] = 0.f;
+            continue;
+        }
+        const int ty0 = (int)floorf(in_y), ty1 = (int)ceilf(in_y);
+        const int tx0 = (int)floorf(in_x), tx1 = (int)ceilf(in_x);
+        const float ly = in_y - (float)ty0, lx = in_x - (float)tx0;
+        const size_t ib = (size_t)(b / K) * H * W;
+        for (int c = 0; c < C; ++c) {
+            const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
+            const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
+            const float top = tl + (tr - tl) * lx;
+            const float bot = bl + (br - bl) * lx;
+            o[c] = top + (bot - top) * ly;
+        }
+    }
+}
+HP3D_KERNEL(256)
+void crop_and_resize_idx_kernel(const float* img, int m, int H, int W, int C, const float* center, const float* scale, const int* idx, int K,
+                                int crop, float* out) {
+    crop_and_resize_idx_body(TapF32{img, C}, m, H, W, C, center, scale, idx, K, crop, out);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_idx_u8_kernel(const unsigned char* img, int m, int H, int W, const float* center, const float* scale, const int* idx,
+                                   int K, int crop, float* out) {
+    crop_and_resize_idx_body(TapU8{img, 3}, m, H, W, 3, center, scale, idx, K, crop, out);
+}
+
+// hand_side / centre / scale of the m slots as dense arrays for the lifting stage and kp_detect: latency only
+HP3D_KERNEL(256)
+void slot_gather_kernel(const int* idx, int m, const float* hand_side, const float* center, const float* scale, float* hand_side_d,
+                        float* center_d, float* scale_d) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+        const int s = idx[i];
+        if (hand_side_d) { hand_side_d[i * 2] = hand_side[s * 2]; hand_side_d[i * 2 + 1] = hand_side[s * 2 + 1]; }
+        if (center_d) { center_d[i * 2] = center[s * 2]; center_d[i * 2 + 1] = center[s * 2 + 1]; }
+        if (scale_d) scale_d[i] = scale[s];
+    }
+}
+
+// Dense results -> the caller's slot layout, absent slots filled with 0: the one bandwidth path of the compacted calls (image_crop
+// 786 KB and kp_scoremap 5.5 MB per slot).  The grid lies over (segment, slot): a segment is SCATTER_SEG_WORDS consecutive words of one
+// array of one slot, so a slot's copy or fill is spread over the chip; consecutive lanes take consecutive 16-byte (vec) or 4-byte words.
+constexpr unsigned SCATTER_SEG_WORDS = 8192;          // 32 KB: 8 rounds of 256 lanes x 16 bytes
+HP3D_KERNEL(256)
+void slot_scatter_kernel(ScatterPlan plan, const int* pos, int ns) {
+    int k = 0;
+    for (int i = 1; i < plan.n; ++i)
+        if (blockIdx.x >= plan.a[i].seg0) k = i;
+    const ScatterArray A = plan.a[k];
+    const unsigned w0 = (blockIdx.x - A.seg0) * SCATTER_SEG_WORDS;
+    const unsigned w1 = min(w0 + SCATTER_SEG_WORDS, A.words);
+    for (int slot = blockIdx.y; slot < ns; slot += gridDim.y) {
+        const int p = pos[slot];
+        float* d = A.dst + (size_t)slot * A.words;
+        const float* sp = A.src + (size_t)(p < 0 ? 0 : p) * A.words;
+        if (A.vec) {
+            for (unsigned w = w0 + threadIdx.x * 4; w < w1; w += 1024) {
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (p >= 0) v = *(const f32x4*)(sp + w);
+                *(f32x4*)(d + w) = v;
+            }
+        } else {
+            // (words, not floats: an int32 or half a float64 must keep its bits)
+            const unsigned* su = (const unsigned*)sp;
+            unsigned* du = (unsigned*)d;
+            for (unsigned w = w0 + threadIdx.x; w < w1; w += 256) du[w] = p >= 0 ? su[w] : 0u;
+        }
+    }
+}
+
+// track_hands_box_kernel behind a compacted back half, one workgroup per slot: kp_image / sm hold the m slots that ran.  A slot that
+// ran (pos >= 0: it is valid) gets track_box_rule on its dense entry; an absent slot holds its box with lost = 0, confidence = 0.
+HP3D_KERNEL(256)
+void track_hands_box_pos_kernel(const double* kp_image, const float* sm, int cs, int H, int W, int crop, float margin, float min_score,
+                                int use_min_score, const int* pos, const float* box_center, const float* box_scale, float* center,
+                                float* scale, float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0) {
+    const int b = blockIdx.x;
+    const int p = pos[b];
+    TrackBox r = {0.f, 0.f, 1.f, 0.f, 0};
+    if (p >= 0) r = track_box_rule(kp_image, sm, cs, p, H, W, crop, margin, min_score, use_min_score);          // (p is uniform over the workgroup)
+    if (threadIdx.x == 0) {
+        const bool v = p >= 0;
+        center[b * 2] = v ? r.cy : box_center[b * 2];
+        center[b * 2 + 1] = v ? r.cx : box_center[b * 2 + 1];
+        scale[b] = v ? r.scale : box_scale[b];
+        confidence[b] = v ? r.conf : 0.f;
+        lost[b] = v ? r.lost : 0;
+        if (keep_next) keep_next[b] = (v && !r.lost) ? 1 : 0;
+        if (detected0) detected0[b] = 0;
+        if (area0) area0[b] = 0;
+        if (claimed0) claimed0[b] = 0;
+    }
+}
+
 inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
     long g = (total + block - 1) / block;
     if (g < 1) g = 1;
@@ -1892,6 +2013,38 @@ void track_hands_box_launch(const double* kp_image, const float* sm, int cs, int
                             int use_min_score, const int* valid, const float* box_center, const float* box_scale, float* center, float* scale,
                             float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0, hipStream_t s) {
     HP3D_LAUNCH(track_hands_box_kernel, dim3(n), dim3(256), 0, s, kp_image, sm, cs, H, W, crop, margin, min_score, use_min_score, valid,
+                box_center, box_scale, center, scale, confidence, lost, keep_next, detected0, area0, claimed0);
+}
+void crop_and_resize_idx_launch(const float* img, int m, int H, int W, int C, const float* center, const float* scale, const int* idx, int K,
+                                int crop, float* out, hipStream_t s) {
+    HP3D_LAUNCH(crop_and_resize_idx_kernel, dim3(grid_for((long)m * crop * crop)), dim3(256), 0, s, img, m, H, W, C, center, scale, idx, K,
+                crop, out);
+}
+void crop_and_resize_idx_u8_launch(const unsigned char* img, int m, int H, int W, const float* center, const float* scale, const int* idx,
+                                   int K, int crop, float* out, hipStream_t s) {
+    HP3D_LAUNCH(crop_and_resize_idx_u8_kernel, dim3(grid_for((long)m * crop * crop)), dim3(256), 0, s, img, m, H, W, center, scale, idx, K,
+                crop, out);
+}
+void slot_gather_launch(const int* idx, int m, const float* hand_side, const float* center, const float* scale, float* hand_side_d,
+                        float* center_d, float* scale_d, hipStream_t s) {
+    HP3D_LAUNCH(slot_gather_kernel, dim3(grid_for(m)), dim3(256), 0, s, idx, m, hand_side, center, scale, hand_side_d, center_d, scale_d);
+}
+void slot_scatter_launch(ScatterPlan plan, const int* pos, int ns, hipStream_t s) {
+    if (plan.n < 1 || ns < 1) return;
+    unsigned segs = 0;
+    for (int i = 0; i < plan.n; ++i) {
+        ScatterArray& a = plan.a[i];
+        a.seg0 = segs;
+        a.vec = !(a.words & 3) && !(((uintptr_t)a.src | (uintptr_t)a.dst) & 15);          // (conv_splitk_reduce_launch's choice)
+        segs += (a.words + SCATTER_SEG_WORDS - 1) / SCATTER_SEG_WORDS;
+    }
+    HP3D_LAUNCH(slot_scatter_kernel, dim3(segs, std::min(ns, 65535)), dim3(256), 0, s, plan, pos, ns);
+}
+void track_hands_box_pos_launch(const double* kp_image, const float* sm, int cs, int n, int H, int W, int crop, float margin, float min_score,
+                                int use_min_score, const int* pos, const float* box_center, const float* box_scale, float* center,
+                                float* scale, float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0,
+                                hipStream_t s) {
+    HP3D_LAUNCH(track_hands_box_pos_kernel, dim3(n), dim3(256), 0, s, kp_image, sm, cs, H, W, crop, margin, min_score, use_min_score, pos,
                 box_center, box_scale, center, scale, confidence, lost, keep_next, detected0, area0, claimed0);
 }
 void track_hands_select_launch(const int* keep, const float* det_center, const float* det_scale, const int* det_valid, const int* det_area,

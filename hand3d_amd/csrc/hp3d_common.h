@@ -475,6 +475,45 @@ void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, f
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s);
 void box_to_detect_launch(const float* center, const float* scale, int n, int f, float* center_d, float* scale_d, hipStream_t s);
+// compaction of absent hand slots (option "hands_compact").  idx [m]: the slots that run, ascending; pos [ns]: a slot's
+// dense index or -1.  Crop i is cut from image idx[i] / K with box idx[i] of the slot-layout center / scale and lands at dense
+// position i (the tap arithmetic of crop_and_resize_kernel / crop_and_resize_u8_kernel, op by op).
+void crop_and_resize_idx_launch(const float* img, int m, int H, int W, int C, const float* center, const float* scale, const int* idx, int K,
+                                int crop, float* out, hipStream_t s);
+void crop_and_resize_idx_u8_launch(const unsigned char* img, int m, int H, int W, const float* center, const float* scale, const int* idx,
+                                   int K, int crop, float* out, hipStream_t s);
+// hand_side [ns,2] / center [ns,2] / scale [ns] of the m slots -> dense arrays (any pair may be null)
+void slot_gather_launch(const int* idx, int m, const float* hand_side, const float* center, const float* scale, float* hand_side_d,
+                        float* center_d, float* scale_d, hipStream_t s);
+// dense results [m, words] -> the slot layout [ns, words]; absent slots are filled with 0.  words = 4-byte words per slot (an int32 or
+// a float is one, a float64 two: bits are copied).  Up to HP3D_SCATTER_MAX arrays in one launch; src and dst must not overlap.
+#define HP3D_SCATTER_MAX 6
+struct ScatterArray {
+    const float* src;
+    float* dst;
+    unsigned words;
+    unsigned seg0;               // (filled by the launcher: the array's first segment of the grid)
+    int vec;                     // (filled by the launcher: 16-byte loads and stores)
+};
+struct ScatterPlan {
+    ScatterArray a[HP3D_SCATTER_MAX];
+    int n = 0;
+    void add(const void* src, void* dst, size_t words) {
+        if (src && dst && words && n < HP3D_SCATTER_MAX) a[n++] = ScatterArray{(const float*)src, (float*)dst, (unsigned)words, 0u, 0};
+    }
+    double bytes(int ns, int m) const {          // read + written
+        double b = 0;
+        for (int i = 0; i < n; ++i) b += 4.0 * a[i].words * ((double)ns + m);
+        return b;
+    }
+};
+void slot_scatter_launch(ScatterPlan plan, const int* pos, int ns, hipStream_t s);
+// track_hands_box_kernel behind a compacted back half: kp_image / sm are dense; a slot with pos >= 0 gets track_box_rule on its dense
+// entry, an absent one holds its box with lost = 0, confidence = 0, keep_next = 0
+void track_hands_box_pos_launch(const double* kp_image, const float* sm, int cs, int n, int H, int W, int crop, float margin, float min_score,
+                                int use_min_score, const int* pos, const float* box_center, const float* box_scale, float* center,
+                                float* scale, float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0,
+                                hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

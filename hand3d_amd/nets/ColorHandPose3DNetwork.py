@@ -135,20 +135,31 @@ class ColorHandPose3DNetwork(object):
         o = self.engine.infer_full(image, hand_side, outputs=('coord3d', 'kp_crop', 'kp_hw', 'scale', 'center'))
         return o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center']
 
-    def inference_hands(self, image, hand_side, max_hands, evaluation=True):
+    def inference_hands(self, image, hand_side, max_hands, evaluation=True, compact=None):
         """ Not in the reference class: inference() for up to `max_hands` (1 ... 4) hands per frame from ONE HandSegNet pass
             (DESIGN.md 4.12).  Hand k of a frame is the k-th object of the detection map in descending peak foreground score;
             hand 0 is inference()'s hand.  `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3]; `hand_side` [B,K,2], one
             row per slot.  Returns inference()'s tuple with a K axis -- hand_scoremap [B,H,W,2], image_crop [B,K,256,256,3],
             scale_crop [B,K], center [B,K,2], keypoints_scoremap [B,K,256,256,21], keypoint_coord3d [B,K,21,3] -- plus
             valid [B,K] (0: the slot holds no hand; its outputs come from the fall-back crop), area [B,K] (pixels of the hand's
-            mask) and keypoint_hw [B,K,21,2] float64 (row, col in the input image). """
+            mask) and keypoint_hw [B,K,21,2] float64 (row, col in the input image).
+            `compact` = True / False sets the engine option "hands_compact", which stays set (None: as it is): True runs everything behind the boxes on the slots
+            that hold a hand only, and a slot with valid = 0 returns zeros behind its box instead of the fall-back crop's results
+            (the call then waits once per chunk for the valid flags). """
         self._check_eval(evaluation)
+        self._compact(compact)
         if np.asarray(image).dtype == np.uint8:
             o = self.engine.infer_hands_u8(image, hand_side, max_hands, H=np.shape(image)[1], W=np.shape(image)[2])
         else:
             o = self.engine.infer_hands(image, hand_side, max_hands)
         return (o['scoremap'], o['crop'], o['scale'], o['center'], o['kpmap'], o['coord3d'], o['valid'], o['area'], o['kp_hw'])
+
+    def _compact(self, compact):
+        """None leaves the engine option "hands_compact" as it is; the option is written only when the value differs from what this
+        object last wrote (every hp3d_set_option drops captured graphs)."""
+        if compact is not None and bool(compact) != getattr(self, '_compact_set', None):
+            self.engine.set_option('hands_compact', '1' if compact else '0')
+            self._compact_set = bool(compact)
 
     def _detect_scale(self, detect_scale):
         if detect_scale is not None:
@@ -175,7 +186,7 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
-    def track_hands(self, image, hand_side, max_hands, detect_scale=None):
+    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None):
         """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
             keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
             A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
@@ -184,8 +195,11 @@ class ColorHandPose3DNetwork(object):
             `image` float32 [B,H,W,3] (x/255-0.5) or uint8 [B,H,W,3]; `hand_side` [B,K,2], one row per slot.
             Returns track()'s tuple with a K axis plus valid [B,K] (0: the slot holds no hand) and area [B,K] (pixels of the
             object where detected = 1).  The engine's `claimed` counters (objects a kept slot claimed on a detect step) are not in the
-            tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track(). """
+            tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track().
+            `compact`: as for inference_hands() -- a slot with valid = 0 costs nothing behind its box and returns zeros there and
+            confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags. """
         self._detect_scale(detect_scale)
+        self._compact(compact)
         step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step
         o = step(image, hand_side, max_hands)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],

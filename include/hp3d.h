@@ -163,6 +163,11 @@ int hp3d_sync(hp3d_ctx* ctx);
  *          "hands_min_area" = "0" (default: off) | N: hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer than N pixels
  *                            instead of reporting them as hands.  A useful value depends on the trained weights: callers calibrate it on
  *                            the `area` every call returns;
+ *          "hands_compact" = "0" (default) | "1": hp3d_infer_hands* and hp3d_track_hands_step* run everything behind the boxes -- crop,
+ *                            PoseNet2D, lifting, heat-map up-sampling, keypoint detection, the tracker's box rule -- on the slots that hold
+ *                            a hand only (valid = 1), at batch m = their number per chunk, and return the absent-slot fill for the others;
+ *                            see "compaction of absent hand slots" below.  "0": every call enqueues what it did without the option.  Anything
+ *                            else: HP3D_ERR_ARG.  The single-hand entry points ignore it;
  *          "f16_impl"     = "h16" (default) | "mfma" | "h16_force": with half-precision trunks (hp3d_finalize_weights dtype 1),
  *                            the 3x3 / stride-1 layers with Cin >= 64 run on the half-precision trunk kernel (conv_h16.hip)
  *                            whenever their grid fills the chip | never (general kernel only) | whenever the shape allows
@@ -358,6 +363,38 @@ int hp3d_boxes_to_frame(hp3d_ctx* ctx, int n, int f, const float* center_d, cons
                         float* scale);
 int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const float* scale, float* center_d, float* scale_d);
 
+/* ---- compaction of absent hand slots (option "hands_compact" = "1") -------------
+ * Per chunk of frames (at most micro_batch / K), idx[0 .. m) = the slots b K + j with valid = 1, ascending: the state's flags on a tracked
+ * step, what the per-slot choice wrote on a detect step, what the multi-hand growth wrote in hp3d_infer_hands* (a slot 0 over an empty
+ * detection map has valid = 0 and does not run).
+ *  - A valid slot idx[i] returns what the same ops give at batch m on frame idx[i] / K, the slot's box and its hand_side: the launches
+ *    are those of any batch of m crops (the kernel plan follows m, so results agree with the option off to the end-to-end tolerances,
+ *    not bit for bit; the crop, centre and scale are bit-equal).
+ *  - An absent slot returns image_crop = kp_scoremap = coord3d = keypoint_hw = 0, keypoint_hw_crop = 0, confidence = 0, lost = detected =
+ *    area = 0 (a policy: the fill values); center / scale_crop stay its fall-back box, and the tracker's state machine is unchanged (the
+ *    slot holds that box with lost = 0).  The only difference to the option off: its confidence is 0, not the fall-back crop's score.
+ *  - hand_scoremap, hand_mask, valid, area (hp3d_infer_hands*) and claimed are what they are with the option off.
+ *  - A chunk without an absent slot takes the uncompacted path (same launches, same bits); a chunk without a hand enqueues nothing behind
+ *    the boxes but the fill.
+ * THE WAIT: on detect steps and in hp3d_infer_hands* the flags exist on the device only, so each chunk copies them to the host and waits
+ * for the stream once (counter "hands_compact_waits") behind its HandSegNet pass -- also on the _dev entry points, which otherwise return
+ * without waiting.  Tracked steps add no stream synchronise: the state's flags are on the host already.  (The idx / pos upload uses two
+ * page-locked buffers in turn; before one is rewritten the host waits for the event behind its last upload -- two compacted chunks ago,
+ * so it can hold the host only in a call of three or more compacted chunks -- and once more when the slot count grows.  Neither is
+ * counted in "hands_compact_waits".)
+ * Profile rows "slot_gather", "crop_and_resize_idx" / "crop_and_resize_idx_u8", "slot_scatter"; counters "hands_compact_slots_run" /
+ * "hands_compact_slots_skipped" / "hands_compact_waits".  The per-op forms (host pointers):
+ * hp3d_crop_and_resize_idx  exactly one of image [B,H,W,3] float32 / image_u8 [B,H,W,3]; center [B K,2], scale [B K]; idx [m] slot indices
+ *                           -> out [m,crop_size,crop_size,3]: crop i = box idx[i] cut from image idx[i] / K (= hp3d_crop_and_resize /
+ *                           hp3d_crop_and_resize_u8 on the gathered frames and boxes, bit for bit)
+ * hp3d_slot_scatter         dense [m,words] (4-byte words), pos [ns] (dense index or -1) -> out [ns,words]: out[s] = dense[pos[s]], 0 where
+ *                           pos[s] = -1.  `out` holds ns words + 4 floats and is read first: what lies behind the last slot must come
+ *                           back untouched.  skew_words in 0 ... 3 shifts the device destination off its 16-byte alignment (the kernel
+ *                           then takes its 4-byte form).                                                                                  */
+int hp3d_crop_and_resize_idx(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int K, const float* center,
+                             const float* scale, const int32_t* idx, int m, int crop_size, float* out);
+int hp3d_slot_scatter(hp3d_ctx* ctx, const float* dense, const int32_t* pos, int ns, int m, int words, int skew_words, float* out);
+
 /* ---- several hands per frame --------------------------------------------------
  * The whole-path calls above keep ONE object of HandSegNet's detection map per image: the one that grows from the arg-max of the
  * foreground score (single_obj_scoremap, utils/general.py:233-268).  These calls return up to K of them, 1 <= K <= HP3D_MAX_HANDS, from
@@ -368,7 +405,7 @@ int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const
  * bit; where the detection map is empty it keeps that call's fall-back box and reports valid = 0.  Slots left over: valid = 0, area = 0,
  * zero mask, the fall-back box of option "empty_reduce".  Per hand, centre / crop size / scale as hp3d_infer_full computes them.  An object
  * the pass cap cuts short leaves its remainder in R, which can come back as a later hand.
- * All B * K slots run through PoseNet2D and the lifting stage, absent ones on their fall-back crop (no compaction: one kernel plan per
+ * All B * K slots run through PoseNet2D and the lifting stage, absent ones on their fall-back crop (no compaction unless option "hands_compact": one kernel plan per
  * call, no host wait); slot j of image b is index b * K + j of every per-hand output.
  * hp3d_infer_hands      image [B,H,W,3], hand_side [B,K,2] (per slot: which hand is left or right is the caller's knowledge) ->
  *                       hand_scoremap [B,H,W,2], image_crop [B,K,256,256,3], scale_crop [B,K], center [B,K,2],
@@ -404,7 +441,7 @@ int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* i
  * slot's hand found again: it is dropped (never tested against "hands_min_area") and counted for the lowest slot that claims it.  The
  * others fill the free slots in the order of discovery, lowest free slot first (detected = valid = 1, box and area as hp3d_infer_hands
  * gives them); free slots left over are absent (valid = 0, area = 0, the fall-back box of option "empty_reduce").  Every growth, claimed
- * or not, counts toward the cap of 4 K growths per image.  Absent slots run the back half on their fall-back crop; their confidence is
+ * or not, counts toward the cap of 4 K growths per image.  Absent slots run the back half on their fall-back crop (unless option "hands_compact"); their confidence is
  * reported, their lost flag is 0, and they keep that box until a detect step fills them.
  * hp3d_track_hands_reset   the next step detects and keeps nothing.
  * hp3d_track_hands_seed    center [B,K,2] (row, col), scale [B,K], valid int32 [B,K]: valid slots need a finite centre and a finite
@@ -519,6 +556,8 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "crop_u8_launches" = crops taken straight from a uint8 frame (tracked steps of hp3d_track_step_u8 / hp3d_track_hands_step_u8, one per chunk; hp3d_crop_and_resize_u8);
  * "detect_scale_steps" = detect steps of hp3d_track_step* / hp3d_track_hands_step* that ran at option "detect_scale" > 1; "arena_bytes" = bytes of
  * the context's frame-sized device buffers (the two activation buffers, image, staging, score map, mask, foreground, detection map);
+ * "hands_compact_slots_run" / "hands_compact_slots_skipped" = slots of hp3d_infer_hands* / hp3d_track_hands_step* chunks whose back half ran / was
+ * skipped under option "hands_compact" = "1", "hands_compact_waits" = stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
