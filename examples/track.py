@@ -28,6 +28,9 @@ if __name__ == '__main__':
                     help='detect steps find the hand on the F x F area mean of the frame and crop from the frame itself (1: detect on the frame)')
     ap.add_argument('--compact', action='store_true',
                     help='with --hands K: slots without a hand cost nothing behind their box and report zeros (DESIGN.md 4.15)')
+    ap.add_argument('--partial-detect', action='store_true',
+                    help='a step that detects because some frames of a batch lost their hand runs HandSegNet on those frames only '
+                         '(DESIGN.md 4.16; single-hand tracking)')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -57,6 +60,7 @@ if __name__ == '__main__':
     net.engine.set_option('track_redetect', str(a.redetect))
     net.engine.set_option('track_min_score', a.min_score)
     net.engine.set_option('detect_scale', str(a.detect_scale))
+    net.engine.set_option('track_partial_detect', '1' if a.partial_detect else '0')
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
     net.track_reset()
     net.track_hands_reset()

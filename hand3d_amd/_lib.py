@@ -82,6 +82,7 @@ _SIGNATURES = {
     'hp3d_slot_scatter': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_gather_frames': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     'hp3d_boxes_to_frame': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'hp3d_boxes_to_detect': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'hp3d_mask_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
@@ -617,6 +618,20 @@ class Engine(object):
         B, H, W, _ = img.shape
         out = np.empty((B, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
         self._chk(self.lib.hp3d_downscale_u8(self.h, _ptr(img), B, H, W, int(f), _ptr(out)))
+        return out
+
+    def gather_frames(self, image, idx, f=1):
+        """The frames idx (strictly ascending) of image [B,H,W,3], as a detect step of option "track_partial_detect" hands them to
+        HandSegNet -> [m,ceil(H/f),ceil(W/f),3] float32: float32 frames copied (f = 1) or downscaled; uint8 frames
+        normalised (x / 255 - 0.5, f = 1) or downscaled as downscale_u8 does."""
+        u8 = np.asarray(image).dtype == np.uint8
+        image = np.ascontiguousarray(image, dtype=np.uint8 if u8 else np.float32)
+        assert image.ndim == 4 and image.shape[3] == 3, "image must be [B,H,W,3]"
+        B, H, W, _ = image.shape
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        out = np.empty((idx.size, -(-H // max(int(f), 1)), -(-W // max(int(f), 1)), 3), np.float32)
+        self._chk(self.lib.hp3d_gather_frames(self.h, None if u8 else _ptr(image), _ptr(image) if u8 else None, B, H, W, int(f),
+                                              _ptr(idx), int(idx.size), _ptr(out)))
         return out
 
     def boxes_to_frame(self, center_d, crop_size_d, f):

@@ -284,6 +284,8 @@ struct Options {
                                     // f x f area mean and crop from the frame itself (1: detect on the frame)
     int hands_compact = 0;          // option "hands_compact": hp3d_infer_hands* / hp3d_track_hands_step* run the back half on the slots that hold a
                                     // hand only; 0: every slot runs, absent ones on their fall-back crop
+    int track_partial_detect = 0;   // option "track_partial_detect": a detect step of hp3d_track_step* that only `lost` flags caused runs HandSegNet,
+                                    // the soft-max and the mask growth on the lost frames only; 0: on the whole batch
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -315,6 +317,8 @@ struct Counters {
     long detect_scale_steps = 0;                    // detect steps of either tracker that ran at detect_scale > 1
     long hands_compact_slots_run = 0, hands_compact_slots_skipped = 0;     // option "hands_compact": slots whose back half ran / was skipped
     long hands_compact_waits = 0;                   // ... and the stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*)
+    long track_partial_frames_run = 0, track_partial_frames_skipped = 0;   // option "track_partial_detect": frames of partial chunks HandSegNet ran on / did not
+    long frame_gather_launches = 0;                 // ... and the launches of frame_gather_kernel (the step and hp3d_gather_frames)
 };
 
 // Option "hands_compact" (DESIGN.md 4.15).  h_map: two page-locked buffers used in turn, idx [cap] | pos [cap] of one chunk; a buffer is
@@ -339,6 +343,7 @@ struct TrackState {
     float* scale[2] = {nullptr, nullptr};
     float* conf = nullptr;
     int *lost = nullptr, *detected = nullptr;
+    int *pidx = nullptr, *ppos = nullptr;      // option "track_partial_detect": per chunk at its offset, the lost frames' indices in the chunk | a frame's dense index
     int* h_lost = nullptr;              // page-locked: the last step's flags (copied behind the step, ev_lost)
     hipEvent_t ev_lost = nullptr;
     bool pending = false;               // that copy has been enqueued and not waited for yet
@@ -1749,6 +1754,8 @@ int ensure_track(hp3d_ctx* ctx, int B) {
     CHK(dev_realloc(ctx, &T.conf, (size_t)B));
     CHK(dev_realloc(ctx, &T.lost, (size_t)B));
     CHK(dev_realloc(ctx, &T.detected, (size_t)B));
+    CHK(dev_realloc(ctx, &T.pidx, (size_t)B));
+    CHK(dev_realloc(ctx, &T.ppos, (size_t)B));
 #ifdef HP3D_EMU
     free(T.h_lost);
     T.h_lost = (int*)malloc(sizeof(int) * (size_t)B);
@@ -1774,6 +1781,8 @@ void track_free(hp3d_ctx* ctx) {
     if (T.conf) hipFree(T.conf);
     if (T.lost) hipFree(T.lost);
     if (T.detected) hipFree(T.detected);
+    if (T.pidx) hipFree(T.pidx);
+    if (T.ppos) hipFree(T.ppos);
 #ifdef HP3D_EMU
     free(T.h_lost);
 #else
@@ -1802,10 +1811,18 @@ int ensure_stage(hp3d_ctx* ctx, size_t floats) {
     return 0;
 }
 // the front of such a detect step: the detection frame into d_image, detection at (nb, Hd, Wd), the boxes of `slots` slots to the frame
+// idx (option "track_partial_detect", K = 0): nb = the number of frames that detect, frame i of them is d_img / d_u8's frame idx[i]; the
+// boxes come out dense
 int run_detect_reduced(hp3d_ctx* ctx, const float* d_img, const unsigned char* d_u8, int nb, int H, int W, int Hd, int Wd, int K = 0,
-                       const MaskKeep& mk = MaskKeep()) {
+                       const MaskKeep& mk = MaskKeep(), const int* idx = nullptr) {
     const int f = ctx->detect_scale, slots = nb * std::max(K, 1);
-    {
+    if (idx) {
+        const char* row = d_u8 ? "downscale_u8_idx" : "downscale_idx";
+        ProfScope ps(ctx, row, row, 0.0, (double)nb * H * W * 3 * (d_u8 ? 1.0 : 4.0) + 4.0 * nb * Hd * Wd * 3);
+        if (d_u8) downscale_u8_idx_launch(d_u8, idx, nb, H, W, f, ctx->d_image, ctx->stream);
+        else downscale_idx_launch(d_img, idx, nb, H, W, f, ctx->d_image, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+    } else {
         const double px = (double)nb * H * W * 3;
         ProfScope ps(ctx, d_u8 ? "downscale_u8" : "downscale", d_u8 ? "downscale_u8" : "downscale", 0.0, px * (d_u8 ? 1.0 : 4.0) + 4.0 * nb * Hd * Wd * 3);
         if (d_u8) downscale_u8_launch(d_u8, nb, H, W, f, ctx->d_image, ctx->stream);
@@ -1830,8 +1847,11 @@ int run_detect_reduced(hp3d_ctx* ctx, const float* d_img, const unsigned char* d
 // derived from its keypoints).  Behind the crop both are infer_full_impl: PoseNet2D, the lifting stage, keypoint detection -- plus
 // the one launch that turns the keypoints into the next boxes.  The step type is decided on the host, before anything is enqueued,
 // from the previous step's `lost` flags (4 * B bytes that travel behind that step); the whole batch detects when any image is lost:
-// one kernel plan per step, no gather of the lost images.  image_u8 (host, frame = network size) instead of image: the tracked
-// step crops straight from the uint8 frame, the detect step normalises it first (preprocess_u8) as hp3d_infer_full_u8 does.
+// one kernel plan per step, no gather of the lost images -- unless option "track_partial_detect" (DESIGN.md 4.16): a detect step that
+// only `lost` flags caused then runs HandSegNet, the soft-max and the mask growth per chunk at batch m = the chunk's lost frames, on
+// those frames (0 < m < nb: "partial"; m = 0: the chunk is enqueued as a tracked chunk; m = nb: as without the option).
+// image_u8 (host, frame = network size) instead of image: the tracked step crops straight from the uint8 frame, the detect step
+// normalises it first (preprocess_u8) as hp3d_infer_full_u8 does.
 // (track_hands_step_impl below repeats this function's frame per slot: a fix to the upload, the chunk loop, the kp_up / kp_work pair or
 //  the copy_out sequence here belongs there as well.)
 int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, const unsigned char* image_u8, const float* hand_side,
@@ -1856,7 +1876,10 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     const int mb0 = auto_micro_batch(ctx, B, Hd, Wd);
     const int mb = mb0 <= 0 ? B : std::min(mb0, B);
     CHK(ensure_arena(ctx, mb, Hd, Wd));
-    if (f > 1 && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    // option "track_partial_detect": only a detect step that `lost` flags alone caused (a fresh or scheduled one re-boxes every image)
+    const bool partial_step = ctx->track_partial_detect && detect && !force_all;
+    // a host float32 frame is staged where the detection frame (f > 1) or the gathered lost frames (a partial chunk) go to d_image
+    if ((f > 1 || partial_step) && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track(ctx, B));
     T.valid = false;                                     // a step that fails half way leaves no boxes behind
     if (image_u8) {
@@ -1874,18 +1897,61 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
         const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
         const float* d_hs = hand_side + (size_t)b0 * 2;
         const unsigned char* d_u8 = image_u8 ? ctx->d_u8 + (size_t)b0 * H * W * 3 : nullptr;
+        int m = nb;                                      // the chunk's frames that detect
+        if (partial_step) {
+            m = 0;
+            for (int b = b0; b < b0 + nb; ++b) m += T.h_lost[b] != 0 ? 1 : 0;
+        }
+        const bool partial = partial_step && m > 0 && m < nb;
+        const bool chunk_detect = detect && m > 0;       // (m = 0: another chunk holds the lost frame; this one runs as a tracked chunk)
         if (!dev) {
             CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * 2, false));
             d_hs = ctx->d_hs;
             if (!image_u8) {
-                float* stage = f > 1 ? ctx->d_stage : ctx->d_image;
+                float* stage = (f > 1 || partial) ? ctx->d_stage : ctx->d_image;
                 CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
                 d_img = stage;
             }
         }
         float* bc = T.center[cur] + (size_t)b0 * 2;
         float* bs = T.scale[cur] + b0;
-        if (detect && f > 1) {
+        int* pidx = T.pidx + b0;
+        int* ppos = T.ppos + b0;
+        if (partial) {           // idx / pos from the flags, which this chunk's track_box has not overwritten yet
+            {
+                ProfScope ps(ctx, "track_partial_index", "track_partial_index", 0.0, 12.0 * nb);
+                track_partial_index_launch(T.lost + b0, nb, pidx, ppos, ctx->stream);
+            }
+            ctx->track_partial_frames_run += m;
+            ctx->track_partial_frames_skipped += nb - m;
+            // the m lost frames, dense, into d_image: never the buffer the chunk's frames lie in (a host frame was staged in d_stage)
+            if (f > 1) {
+                CHK(run_detect_reduced(ctx, d_img, d_u8, m, H, W, Hd, Wd, 0, MaskKeep(), pidx));
+            } else {
+                if (image_u8) {
+                    ProfScope ps(ctx, "preprocess_u8_idx", "preprocess_u8_idx", 0.0, 5.0 * m * H * W * 3);
+                    preprocess_u8_idx_launch(d_u8, pidx, m, H, W, ctx->d_image, ctx->stream);
+                } else {
+                    ProfScope ps(ctx, "frame_gather", "frame_gather", 0.0, 8.0 * m * H * W * 3);
+                    frame_gather_launch(d_img, pidx, m, (size_t)H * W * 3, ctx->d_image, ctx->stream);
+                    ++ctx->frame_gather_launches;
+                }
+                HIPCHK(ctx, hipGetLastError());
+                CHK(run_detect_and_crop(ctx, ctx->d_image, m, H, W, 0, true, false));
+            }
+            {
+                ProfScope ps(ctx, "track_select_pos", "track_select_pos", 0.0, 16.0 * nb);
+                track_select_pos_launch(T.lost + b0, ppos, ctx->d_center, ctx->d_scale, nb, bc, bs, T.detected + b0, ctx->stream);
+            }
+            if (image_u8) {          // all nb crops straight from the uint8 frame (= normalise, then crop: bit for bit)
+                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
+                crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
+                ++ctx->crop_u8_launches;
+            } else {
+                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
+                crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
+            }
+        } else if (chunk_detect && f > 1) {
             CHK(run_detect_reduced(ctx, d_img, d_u8, nb, H, W, Hd, Wd));
             {
                 ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
@@ -1899,7 +1965,7 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
                 ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
                 crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
             }
-        } else if (detect) {
+        } else if (chunk_detect) {
             if (image_u8) {
                 ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
                 preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
@@ -1938,7 +2004,7 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
             ProfScope ps(ctx, "track_box", "track_box", 0.0, 4.0 * nb * 32 * 32 * 21);
             track_box_launch(dev && kpi_out ? kpi_out : ctx->d_kpimg, ctx->d_sm[2], 32, nb, H, W, 256, ctx->track_margin, ctx->track_min_score,
                              ctx->track_use_min_score, T.center[nxt] + (size_t)b0 * 2, T.scale[nxt] + b0, T.conf + b0, T.lost + b0,
-                             detect ? nullptr : T.detected + b0, ctx->stream);
+                             chunk_detect ? nullptr : T.detected + b0, ctx->stream);
             return 0;
         };
         CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, nb, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
@@ -2787,6 +2853,11 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
         ctx->hands_compact = v == "1";
         return 0;
     }
+    if (k == "track_partial_detect") {
+        if (v != "0" && v != "1") HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_partial_detect wants 0 or 1, got %s", value);
+        ctx->track_partial_detect = v == "1";
+        return 0;
+    }
     if (k == "track_redetect") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -3433,6 +3504,35 @@ int hp3d_downscale_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int 
     return downscale_impl(ctx, nullptr, image_u8, B, H, W, f, out);
 }
 
+// ---- detection on the lost frames only: the per-op form ---------------------------------------------------
+int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int f, const int32_t* idx, int m,
+                       float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if ((image != nullptr) == (image_u8 != nullptr)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "gather_frames: exactly one of image / image_u8");
+    if (!idx || !out || B < 1 || H < 1 || W < 1 || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (m < 1 || m > B) HP3D_FAIL(ctx, HP3D_ERR_ARG, "gather_frames: m = %d must be in 1 ... B = %d", m, B);
+    for (int i = 0; i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B || (i > 0 && idx[i] <= idx[i - 1]))
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "gather_frames: idx[%d] = %d: idx must be strictly ascending in [0, %d)", i, (int)idx[i], B);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const size_t ni = (size_t)B * H * W * 3, no = (size_t)m * Hd * Wd * 3;
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    int32_t* d_i = S.upload(idx, (size_t)m); NN(ctx, d_i);
+    if (image_u8) {
+        unsigned char* d_x = S.upload(image_u8, ni); NN(ctx, d_x);
+        if (f > 1) downscale_u8_idx_launch(d_x, d_i, m, H, W, f, d_o, ctx->stream);
+        else preprocess_u8_idx_launch(d_x, d_i, m, H, W, d_o, ctx->stream);
+    } else {
+        float* d_x = S.upload(image, ni); NN(ctx, d_x);
+        if (f > 1) downscale_idx_launch(d_x, d_i, m, H, W, f, d_o, ctx->stream);
+        else { frame_gather_launch(d_x, d_i, m, (size_t)H * W * 3, d_o, ctx->stream); ++ctx->frame_gather_launches; }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
 int hp3d_boxes_to_frame(hp3d_ctx* ctx, int n, int f, const float* center_d, const float* crop_size_d, float* center, float* crop_size,
                         float* scale) {
     if (!ctx) return HP3D_ERR_ARG;
@@ -3835,6 +3935,9 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"hands_compact_slots_run", &Counters::hands_compact_slots_run, false},
         {"hands_compact_slots_skipped", &Counters::hands_compact_slots_skipped, false},
         {"hands_compact_waits", &Counters::hands_compact_waits, false},
+        {"track_partial_frames_run", &Counters::track_partial_frames_run, false},
+        {"track_partial_frames_skipped", &Counters::track_partial_frames_skipped, false},
+        {"frame_gather_launches", &Counters::frame_gather_launches, false},
     };
     const std::string k(name);
     for (const auto& c : table)

@@ -1616,8 +1616,11 @@ template <typename T> struct DownAcc { typedef float type; };
 template <> struct DownAcc<unsigned char> { typedef unsigned type; };
 __device__ __forceinline__ float downscale_finish(float sum, float n) { return sum / n; }
 __device__ __forceinline__ float downscale_finish(unsigned sum, float n) { return ((float)sum / n) / 255.0f - 0.5f; }
-template <typename T, int F>
-__device__ __forceinline__ void downscale_body(const T* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+// IDX (option "track_partial_detect"): output frame b is built from source frame idx[b] -- B = the number of output frames.
+// A frame is H row pitches long, so where the base and the row pitch are multiples of ALIGN (`wide`) every selected frame's base is one too.
+template <typename T, int F, bool IDX = false>
+__device__ __forceinline__ void downscale_body(const T* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
+                                               const int* idx = nullptr) {
     typedef typename DownAcc<T>::type acc_t;
     constexpr int NV = F > 0 ? F * 3 : 1;
     constexpr int ROWB = NV * (int)sizeof(T);
@@ -1630,7 +1633,8 @@ __device__ __forceinline__ void downscale_body(const T* img, int B, int H, int W
         const int b = (int)(r / Hd);
         const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
         acc_t s0 = 0, s1 = 0, s2 = 0;
-        const T* p = img + (((size_t)b * H + y0) * W + x0) * 3;
+        const int sb = IDX ? idx[b] : b;
+        const T* p = img + (((size_t)sb * H + y0) * W + x0) * 3;
         for (int yy = y0; yy < y1; ++yy, p += (size_t)W * 3) {
             if (F > 0 && wide && nx == F) {
                 T v[NV];
@@ -1655,6 +1659,16 @@ template <int F>
 HP3D_KERNEL(256)
 void downscale_u8_kernel(const unsigned char* img, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
     downscale_body<unsigned char, F>(img, B, H, W, f, Hd, Wd, wide, out);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_idx_kernel(const float* img, const int* idx, int m, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_body<float, F, true>(img, m, H, W, f, Hd, Wd, wide, out, idx);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_u8_idx_kernel(const unsigned char* img, const int* idx, int m, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_body<unsigned char, F, true>(img, m, H, W, f, Hd, Wd, wide, out, idx);
 }
 
 // A detection-frame box (centre_d, crop_size_d) in frame coordinates: centre = centre_d * f + (f - 1) / 2 (the centre of detection pixel
@@ -1803,6 +1817,93 @@ void track_hands_box_pos_kernel(const double* kp_image, const float* sm, int cs,
         if (detected0) detected0[b] = 0;
         if (area0) area0[b] = 0;
         if (claimed0) claimed0[b] = 0;
+    }
+}
+
+// ---- detection on the lost frames only (option "track_partial_detect") ------------------------------------------------
+// A detect step that only `lost` flags caused runs HandSegNet, the soft-max and the mask growth at batch m = the chunk's lost frames.
+// idx [m] = those frames' indices in the chunk, ascending; pos [n] = a frame's dense index, -1 for one that keeps its tracked box.
+//
+// The two lists from the chunk's flags, on the device (the host knows m from its copy of the same flags): ONE workgroup walks the n flags
+// 256 at a time -- an inclusive scan of the tile in LDS, the running count carried from tile to tile -- so any n works.
+HP3D_KERNEL(256)
+void track_partial_index_kernel(const int* lost, int n, int* idx, int* pos) {
+    __shared__ int part[256];
+    const int t = threadIdx.x;
+    int base = 0;
+    for (int b0 = 0; b0 < n; b0 += 256) {          // (uniform trip count: every lane reaches every barrier)
+        const int b = b0 + t;
+        const int flag = (b < n && lost[b] != 0) ? 1 : 0;
+        part[t] = flag;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const int v = t >= d ? part[t - d] : 0;
+            __syncthreads();
+            part[t] += v;
+            __syncthreads();
+        }
+        const int incl = part[t], tot = part[255];
+        if (b < n) {
+            const int p = base + incl - 1;
+            pos[b] = flag ? p : -1;
+            if (flag) idx[p] = b;
+        }
+        base += tot;
+        __syncthreads();          // part is rewritten by the next tile
+    }
+}
+
+// out[i] = frames[idx[i]], i < m; a frame is `words` units of VEC floats.  VEC = 4: 16-byte loads and stores (the frame's bytes a multiple
+// of 16 and both bases 16-byte aligned, so every frame's base is); VEC = 1: 4 bytes.  The grid lies over (piece of a frame, frame);
+// consecutive lanes take consecutive units.  src and dst must not overlap.
+template <int VEC>
+HP3D_KERNEL(256)
+void frame_gather_kernel(const float* frames, const int* idx, int m, size_t words, float* out) {
+    typedef typename std::conditional<VEC == 4, f32x4, float>::type vec_t;
+    for (int i = blockIdx.y; i < m; i += gridDim.y) {
+        const vec_t* sp = (const vec_t*)(frames + (size_t)idx[i] * words * VEC);
+        vec_t* dp = (vec_t*)(out + (size_t)i * words * VEC);
+        for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (size_t)gridDim.x * blockDim.x) dp[w] = sp[w];
+    }
+}
+
+// preprocess_u8_kernel at equal sizes on the frames idx[i] only: out[i] = x / 255 - 0.5 of frame idx[i], float32 op by op (at equal sizes
+// that kernel's result is its top-left tap); a frame is `words` units of VEC elements.  VEC = 4: one 4-byte load and one 16-byte store
+// per lane (the frame's element count a multiple of 4, the source base 4-byte and the destination 16-byte aligned, so every frame's
+// are); VEC = 1: element by element.
+template <int VEC>
+HP3D_KERNEL(256)
+void preprocess_u8_idx_kernel(const unsigned char* img, const int* idx, int m, size_t words, float* out) {
+    for (int i = blockIdx.y; i < m; i += gridDim.y) {
+        const unsigned char* sp = img + (size_t)idx[i] * words * VEC;
+        float* dp = out + (size_t)i * words * VEC;
+        for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (size_t)gridDim.x * blockDim.x) {
+            if (VEC == 4) {
+                unsigned char v[4];
+                __builtin_memcpy(v, __builtin_assume_aligned(sp + w * 4, 4), 4);
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (float)v[e] / 255.0f - 0.5f;
+                *(f32x4*)(dp + w * 4) = o;
+            } else {
+                dp[w] = (float)sp[w] / 255.0f - 0.5f;
+            }
+        }
+    }
+}
+
+// track_select_kernel where HandSegNet ran on the lost frames only: det_center / det_scale are dense, image b's entry is pos[b].
+HP3D_KERNEL(256)
+void track_select_pos_kernel(const int* lost_prev, const int* pos, const float* det_center, const float* det_scale, int B,
+                             float* box_center, float* box_scale, int* detected) {
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+        const int d = lost_prev[b] != 0 ? 1 : 0;
+        if (d) {
+            const int p = pos[b];
+            box_center[b * 2] = det_center[p * 2]; box_center[b * 2 + 1] = det_center[p * 2 + 1];
+            box_scale[b] = det_scale[p];
+        }
+        detected[b] = d;
     }
 }
 
@@ -2052,24 +2153,65 @@ void track_hands_select_launch(const int* keep, const float* det_center, const f
     HP3D_LAUNCH(track_hands_select_kernel, dim3(grid_for(n)), dim3(256), 0, s, keep, det_center, det_scale, det_valid, det_area, n,
                 box_center, box_scale, valid, detected, area);
 }
+void track_partial_index_launch(const int* lost, int n, int* idx, int* pos, hipStream_t s) {
+    HP3D_LAUNCH(track_partial_index_kernel, dim3(1), dim3(256), 0, s, lost, n, idx, pos);
+}
+void frame_gather_launch(const float* frames, const int* idx, int m, size_t frame_floats, float* out, hipStream_t s) {
+    if (m < 1 || frame_floats < 1) return;
+    const bool vec = !(frame_floats & 3) && !(((uintptr_t)frames | (uintptr_t)out) & 15);
+    const size_t words = vec ? frame_floats / 4 : frame_floats;
+    const dim3 grid(grid_for((long)words, 256, 1024), std::min(m, 65535)), block(256);
+    if (vec) HP3D_LAUNCH(frame_gather_kernel<4>, grid, block, 0, s, frames, idx, m, words, out);
+    else HP3D_LAUNCH(frame_gather_kernel<1>, grid, block, 0, s, frames, idx, m, words, out);
+}
+void preprocess_u8_idx_launch(const unsigned char* img, const int* idx, int m, int H, int W, float* out, hipStream_t s) {
+    if (m < 1) return;
+    const size_t n = (size_t)H * W * 3;
+    const bool vec = !(n & 3) && !((uintptr_t)img & 3) && !((uintptr_t)out & 15);
+    const size_t words = vec ? n / 4 : n;
+    const dim3 grid(grid_for((long)words, 256, 1024), std::min(m, 65535)), block(256);
+    if (vec) HP3D_LAUNCH(preprocess_u8_idx_kernel<4>, grid, block, 0, s, img, idx, m, words, out);
+    else HP3D_LAUNCH(preprocess_u8_idx_kernel<1>, grid, block, 0, s, img, idx, m, words, out);
+}
+void track_select_pos_launch(const int* lost_prev, const int* pos, const float* det_center, const float* det_scale, int B,
+                             float* box_center, float* box_scale, int* detected, hipStream_t s) {
+    HP3D_LAUNCH(track_select_pos_kernel, dim3(grid_for(B)), dim3(256), 0, s, lost_prev, pos, det_center, det_scale, B, box_center,
+                box_scale, detected);
+}
 // T = float | unsigned char; the wide form where f is 2, 4 or 8 and every window row starts on the load's alignment
-template <typename T, class K0, class K2, class K4, class K8>
-static void downscale_dispatch(K0 k0, K2 k2, K4 k4, K8 k8, const T* img, int B, int H, int W, int f, float* out, hipStream_t s) {
-    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+template <typename T>
+static int downscale_wide(const T* img, int W, int f) {
     const int rowb = f * 3 * (int)sizeof(T);
     const int align = rowb % 16 == 0 ? 16 : rowb % 8 == 0 ? 8 : rowb % 4 == 0 ? 4 : rowb % 2 == 0 ? 2 : 1;
-    const int wide = ((uintptr_t)img % align == 0 && ((size_t)W * 3 * sizeof(T)) % align == 0) ? 1 : 0;
-    const dim3 grid(grid_for((long)B * Hd * Wd)), block(256);
-    if (f == 2) HP3D_LAUNCH(k2, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
-    else if (f == 4) HP3D_LAUNCH(k4, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
-    else if (f == 8) HP3D_LAUNCH(k8, grid, block, 0, s, img, B, H, W, f, Hd, Wd, wide, out);
-    else HP3D_LAUNCH(k0, grid, block, 0, s, img, B, H, W, f, Hd, Wd, 0, out);
+    return ((uintptr_t)img % align == 0 && ((size_t)W * 3 * sizeof(T)) % align == 0) ? 1 : 0;
+}
+// One dispatcher for both forms: `lead...` = (B) for the kernels over the whole batch, (idx, m) for the indexed ones -- where the same
+// test holds: a frame is H row pitches long, so every selected frame's base is aligned as the first one's.
+template <typename T, class K0, class K2, class K4, class K8, class... Lead>
+static void downscale_dispatch(K0 k0, K2 k2, K4 k4, K8 k8, const T* img, int frames, int H, int W, int f, float* out, hipStream_t s,
+                               Lead... lead) {
+    if (frames < 1) return;
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const int wide = downscale_wide(img, W, f);
+    const dim3 grid(grid_for((long)frames * Hd * Wd)), block(256);
+    if (f == 2) HP3D_LAUNCH(k2, grid, block, 0, s, img, lead..., H, W, f, Hd, Wd, wide, out);
+    else if (f == 4) HP3D_LAUNCH(k4, grid, block, 0, s, img, lead..., H, W, f, Hd, Wd, wide, out);
+    else if (f == 8) HP3D_LAUNCH(k8, grid, block, 0, s, img, lead..., H, W, f, Hd, Wd, wide, out);
+    else HP3D_LAUNCH(k0, grid, block, 0, s, img, lead..., H, W, f, Hd, Wd, 0, out);
+}
+void downscale_idx_launch(const float* img, const int* idx, int m, int H, int W, int f, float* out, hipStream_t s) {
+    downscale_dispatch(downscale_idx_kernel<0>, downscale_idx_kernel<2>, downscale_idx_kernel<4>, downscale_idx_kernel<8>, img, m, H, W, f,
+                       out, s, idx, m);
+}
+void downscale_u8_idx_launch(const unsigned char* img, const int* idx, int m, int H, int W, int f, float* out, hipStream_t s) {
+    downscale_dispatch(downscale_u8_idx_kernel<0>, downscale_u8_idx_kernel<2>, downscale_u8_idx_kernel<4>, downscale_u8_idx_kernel<8>, img,
+                       m, H, W, f, out, s, idx, m);
 }
 void downscale_launch(const float* img, int B, int H, int W, int f, float* out, hipStream_t s) {
-    downscale_dispatch(downscale_kernel<0>, downscale_kernel<2>, downscale_kernel<4>, downscale_kernel<8>, img, B, H, W, f, out, s);
+    downscale_dispatch(downscale_kernel<0>, downscale_kernel<2>, downscale_kernel<4>, downscale_kernel<8>, img, B, H, W, f, out, s, B);
 }
 void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, float* out, hipStream_t s) {
-    downscale_dispatch(downscale_u8_kernel<0>, downscale_u8_kernel<2>, downscale_u8_kernel<4>, downscale_u8_kernel<8>, img, B, H, W, f, out, s);
+    downscale_dispatch(downscale_u8_kernel<0>, downscale_u8_kernel<2>, downscale_u8_kernel<4>, downscale_u8_kernel<8>, img, B, H, W, f, out, s, B);
 }
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s) {

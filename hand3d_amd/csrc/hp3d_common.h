@@ -475,6 +475,18 @@ void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, f
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s);
 void box_to_detect_launch(const float* center, const float* scale, int n, int f, float* center_d, float* scale_d, hipStream_t s);
+// detection on the lost frames only (option "track_partial_detect").  idx [m]: the chunk's lost frames, ascending; pos [n]:
+// a frame's dense index or -1 -- both built on the device from the n `lost` flags by one workgroup.  frame_gather: out[i] = frames[idx[i]]
+// (frame_floats floats each; 16-byte form where the frame size and both bases allow, else 4-byte; no overlap).  preprocess_u8_idx:
+// preprocess_u8 at equal sizes on the frames idx[i].  downscale_idx / downscale_u8_idx: downscale / downscale_u8 on the frames idx[i].
+// track_select_pos: track_select (force_all = 0) with dense det_center / det_scale, image b's entry at pos[b].
+void track_partial_index_launch(const int* lost, int n, int* idx, int* pos, hipStream_t s);
+void frame_gather_launch(const float* frames, const int* idx, int m, size_t frame_floats, float* out, hipStream_t s);
+void preprocess_u8_idx_launch(const unsigned char* img, const int* idx, int m, int H, int W, float* out, hipStream_t s);
+void downscale_idx_launch(const float* img, const int* idx, int m, int H, int W, int f, float* out, hipStream_t s);
+void downscale_u8_idx_launch(const unsigned char* img, const int* idx, int m, int H, int W, int f, float* out, hipStream_t s);
+void track_select_pos_launch(const int* lost_prev, const int* pos, const float* det_center, const float* det_scale, int B,
+                             float* box_center, float* box_scale, int* detected, hipStream_t s);
 // compaction of absent hand slots (option "hands_compact").  idx [m]: the slots that run, ascending; pos [ns]: a slot's
 // dense index or -1.  Crop i is cut from image idx[i] / K with box idx[i] of the slot-layout center / scale and lands at dense
 // position i (the tap arithmetic of crop_and_resize_kernel / crop_and_resize_u8_kernel, op by op).

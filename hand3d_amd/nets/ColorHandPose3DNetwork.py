@@ -165,7 +165,7 @@ class ColorHandPose3DNetwork(object):
         if detect_scale is not None:
             self.engine.set_option('detect_scale', str(int(detect_scale)))
 
-    def track(self, image, hand_side, detect_scale=None):
+    def track(self, image, hand_side, detect_scale=None, partial_detect=None):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
             HandSegNet as inference() does; every other call crops with the box the dataset readers' hand_crop rule
@@ -175,8 +175,13 @@ class ColorHandPose3DNetwork(object):
             box this step used) -- plus confidence [B], lost [B] (1: the next step will detect again) and detected [B]
             (1: this step's box came from HandSegNet).
             `detect_scale` = f in 1 ... 8 sets the engine option of that name, which stays set (None: as it is): a detect step finds the
-            hand on the frame's f x f area mean and crops from the frame itself; the outputs keep their shapes. """
+            hand on the frame's f x f area mean and crops from the frame itself; the outputs keep their shapes.
+            `partial_detect` = True / False sets the engine option "track_partial_detect", which stays set (None: as it is): a step
+            that detects because some frames of the batch lost their hand runs HandSegNet on those frames only; the others keep
+            their tracked box and come out bit-equal to a step without the option. """
         self._detect_scale(detect_scale)
+        if partial_detect is not None:
+            self.engine.set_option('track_partial_detect', '1' if partial_detect else '0')
         step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
         o = step(image, hand_side)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],

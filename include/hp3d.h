@@ -153,6 +153,10 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            value depends on the trained weights: callers calibrate it on the confidence the steps return;
  *          "track_redetect" = "0" (default: never) | N: every N-th tracking step is a detect step that re-boxes every image
  *                            (hp3d_track_hands_step*: that fills free slots only, kept slots are not re-boxed);
+ *          "track_partial_detect" = "0" (default) | "1": a detect step of hp3d_track_step / _dev / _u8 that only `lost` flags caused runs
+ *                            HandSegNet, the soft-max and the mask growth on the lost frames only, at batch m = their number per chunk; see
+ *                            "partial detection" below.  "0": every call enqueues what it did without the option.  Anything else:
+ *                            HP3D_ERR_ARG.  hp3d_track_hands_step* and every hp3d_infer_* call IGNORE the option;
  *          "detect_scale" = "1" (default) | "2" ... "8", an integer f: the DETECT steps of hp3d_track_step* / hp3d_track_hands_step* find the
  *                            hand on the frame's f x f area mean ([ceil(H/f), ceil(W/f)], at least 16 x 16: HP3D_ERR_ARG before any launch
  *                            otherwise) and crop from the frame itself; see "detection on a reduced frame" below.  "1": detect on the
@@ -297,9 +301,9 @@ int hp3d_pose3d(hp3d_ctx* ctx, int B, const float* scoremap32, const float* hand
  * step's predicted keypoints, and runs no HandSegNet, soft-max or mask growth ("tracked step").  A "detect step" runs them for the
  * whole batch as hp3d_infer_full does and then, per image, keeps the tracked box where the previous step did not flag it as lost.
  * A step detects: the first time after hp3d_create / hp3d_track_reset / a change of (B, H, W); when the previous step flagged ANY
- * image as lost (the whole batch detects: one kernel plan per step, no gather); and, with option "track_redetect" = N > 0, every
- * N-th step (a scheduled re-detection takes HandSegNet's box for every image).  The decision is taken on the host from the previous
- * step's flags before anything is enqueued; a tracked step needs no HandSegNet weights.
+ * image as lost (the whole batch detects: one kernel plan per step, no gather -- unless option "track_partial_detect"); and, with
+ * option "track_redetect" = N > 0, every N-th step (a scheduled re-detection takes HandSegNet's box for every image).  The decision
+ * is taken on the host from the previous step's flags before anything is enqueued; a tracked step needs no HandSegNet weights.
  * hp3d_track_reset    the next step detects.
  * hp3d_track_seed     start from boxes the caller has (another detector, ground truth): center [B,2] (row, col) finite, scale [B] > 0;
  *                     the next step for (B, H, W) is a tracked step.
@@ -362,6 +366,33 @@ int hp3d_downscale_u8(hp3d_ctx* ctx, const uint8_t* image_u8, int B, int H, int 
 int hp3d_boxes_to_frame(hp3d_ctx* ctx, int n, int f, const float* center_d, const float* crop_size_d, float* center, float* crop_size,
                         float* scale);
 int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const float* scale, float* center_d, float* scale_d);
+
+/* ---- partial detection (option "track_partial_detect" = "1") --------------------
+ * hp3d_track_step / _dev / _u8 only.  Which steps detect is unchanged; a fresh step and a scheduled one (option "track_redetect") re-box
+ * every image and run as without the option.  In a detect step that only `lost` flags caused, per chunk of nb frames (the micro-batch
+ * limit stays), with L = the chunk's frames whose previous `lost` flag is set, ascending, m = |L|:
+ *  - m = nb: the chunk runs as without the option (same launches, same bits).
+ *  - m = 0 (another chunk holds the lost frame): the chunk is enqueued as a tracked chunk -- no HandSegNet, soft-max or mask growth,
+ *    hp3d_track_step_u8 crops straight from the uint8 frame -- and detected = 0.
+ *  - 0 < m < nb: HandSegNet, the soft-max and the mask growth run at batch m on the frames of L; crop, PoseNet2D, lifting, keypoint
+ *    detection and the box rule run at batch nb as always.  A frame of L gets the box the same ops give on a batch made of those m
+ *    frames -- at "detect_scale" = 1 hp3d_infer_full's center / scale_crop on the gathered frames bit for bit, at f > 1 the chain
+ *    hp3d_downscale[_u8] -> hp3d_handsegnet -> hp3d_mask_from_scoremap -> hp3d_boxes_to_frame on them -- and detected = 1.  Any other
+ *    frame keeps its tracked box bit for bit, detected = 0, and EVERY output of it is bit-equal to the same step with the option off.
+ *    The frames of L agree with the option-off step to the end-to-end tolerances only: HandSegNet's kernel plan follows m.
+ *    hp3d_track_step_u8 at f = 1 normalises the m frames only and crops all nb straight from the uint8 frame (counted in
+ *    "crop_u8_launches"; bit-identical to normalise-then-crop); at f > 1 only the m detection frames are built.
+ * The step is a detect step like any other: it needs HandSegNet weights, counts once in "track_detect_steps" (and "detect_scale_steps"),
+ * and the schedule of "track_redetect" restarts.  The lists L / positions are built on the device from the flags the previous step left
+ * there; the host learns m from its own copy of the same flags: no wait is added and nothing is read back.
+ * Profile rows "track_partial_index", "frame_gather", "preprocess_u8_idx", "downscale_idx" / "downscale_u8_idx", "track_select_pos";
+ * counters "track_partial_frames_run" / "track_partial_frames_skipped" / "frame_gather_launches".  The per-op form (host pointers):
+ * hp3d_gather_frames  exactly one of image [B,H,W,3] float32 / image_u8 [B,H,W,3]; f in 1 ... 8; idx [m] strictly ascending in [0, B),
+ *                     1 <= m <= B -> out [m,ceil(H/f),ceil(W/f),3]: bit for bit what hp3d_downscale / hp3d_downscale_u8 (f > 1),
+ *                     hp3d_preprocess_u8 at equal sizes (uint8, f = 1) or a plain copy (float32, f = 1) give on the gathered frames.
+ *                     Anything else: HP3D_ERR_ARG before any launch.                                                              */
+int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int f, const int32_t* idx, int m,
+                       float* out);
 
 /* ---- compaction of absent hand slots (option "hands_compact" = "1") -------------
  * Per chunk of frames (at most micro_batch / K), idx[0 .. m) = the slots b K + j with valid = 1, ascending: the state's flags on a tracked
@@ -558,6 +589,9 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * the context's frame-sized device buffers (the two activation buffers, image, staging, score map, mask, foreground, detection map);
  * "hands_compact_slots_run" / "hands_compact_slots_skipped" = slots of hp3d_infer_hands* / hp3d_track_hands_step* chunks whose back half ran / was
  * skipped under option "hands_compact" = "1", "hands_compact_waits" = stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*);
+ * "track_partial_frames_run" / "track_partial_frames_skipped" = frames of hp3d_track_step* chunks that ran partially under option
+ * "track_partial_detect" = "1" (0 < m < nb) on which HandSegNet ran / did not run, "frame_gather_launches" = launches of the float32 frame
+ * gather (those chunks at "detect_scale" = 1 on float32 frames; hp3d_gather_frames on float32 frames at f = 1);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
