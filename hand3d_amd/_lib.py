@@ -54,6 +54,9 @@ _SIGNATURES = {
     'hp3d_pose3d': (C.c_int, [_ctx, C.c_int] + [C.c_void_p] * 5),
     'hp3d_conv2d': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_conv2d_f16': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_first_block_f16': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'hp3d_maxpool2': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_avgpool8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_resize_bilinear': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -733,6 +736,28 @@ class Engine(object):
         out = np.empty((B, Ho, Wo, Cout), np.float32)
         self._chk(self.lib.hp3d_conv2d(self.h, _ptr(x), B, H, W, Cin, _ptr(w), _ptr(b), k, stride, Cout, int(act),
                                        int(pool), _ptr(out)))
+        return out
+
+    def conv2d_f16(self, x, w, b, stride=1, act=True, pool=False, out_f32=False):
+        """One layer of a half-precision trunk (hp3d_conv2d_f16): float32 in and out, half operands and (unless out_f32) a half result."""
+        x, w, b = _f32(x), _f32(w), _f32(b)
+        B, H, W, Cin = x.shape
+        k, _, _, Cout = w.shape
+        Ho, Wo = -(-H // stride), -(-W // stride)
+        if pool:
+            Ho, Wo = Ho // 2, Wo // 2
+        out = np.empty((B, Ho, Wo, Cout), np.float32)
+        self._chk(self.lib.hp3d_conv2d_f16(self.h, _ptr(x), B, H, W, Cin, _ptr(w), _ptr(b), k, stride, Cout, int(act),
+                                           int(pool), int(out_f32), _ptr(out)))
+        return out
+
+    def first_block_f16(self, image, w1, b1, w2, b2):
+        """conv1_1 + conv1_2 + 2x2 max-pool of a half-precision trunk (hp3d_first_block_f16): image [B,H,W,3] -> [B,H/2,W/2,64]."""
+        image, w1, b1, w2, b2 = _f32(image), _f32(w1), _f32(b1), _f32(w2), _f32(b2)
+        B, H, W, c3 = image.shape
+        assert c3 == 3 and w1.shape == (3, 3, 3, 64) and w2.shape == (3, 3, 64, 64) and b1.shape == (64,) and b2.shape == (64,)
+        out = np.empty((B, H // 2, W // 2, 64), np.float32)
+        self._chk(self.lib.hp3d_first_block_f16(self.h, _ptr(image), B, H, W, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out)))
         return out
 
     def maxpool2(self, x):

@@ -1070,13 +1070,15 @@ int run_pw2(hp3d_ctx* ctx, const ConvL& l1, const ConvL& l2, const float* in, in
 
 // Half-precision trunks: conv1_1 (3 -> 64) + conv1_2 (64 -> 64) + 2x2 max-pool as ONE launch of conv_h16.hip's fused form
 // (conv1_1's activation never reaches HBM).  Returns 1 if it ran, 0 if the shape / options do not allow it.
-int run_fused12(hp3d_ctx* ctx, const ConvL& l1, const ConvL& l2, const float* image, int B, int H, int W, float* out, int* oh, int* ow) {
-    if (!ctx->prec || !ctx->use_h16 || !ctx->fuse12 || ctx->conv_naive || l1.mode != 1 || l2.mode != 0 || l1.cout != 64 || l2.cout != 64 ||
+// wts: the blobs the two layers' offsets refer to; f16: the caller's precision (the fused form exists in half precision only).
+int run_fused12(hp3d_ctx* ctx, const ConvW& wts, int f16, const ConvL& l1, const ConvL& l2, const float* image, int B, int H, int W, float* out,
+                int* oh, int* ow) {
+    if (!f16 || !ctx->use_h16 || !ctx->fuse12 || ctx->conv_naive || l1.mode != 1 || l2.mode != 0 || l1.cout != 64 || l2.cout != 64 ||
         !l1.relu || !l2.relu || ((H | W) & 1) || ((uintptr_t)out & 15) ||
         !conv_h16_eligible(ctx->use_h16, l2.k, l2.stride, l2.cin_pad16 / 2, l2.cout_pad, H, W, B, 0, 64))
         return 0;
-    ConvParams p = conv_params(image, (const float*)(ctx->blob16 + l2.w16_off), ctx->blob + l2.b_off, out, B, H, W, H, W, l2.cin_pad16 / 2, 3, 64, 64, 64, 1, 1, 1);
-    p.wpk1 = ctx->blob + l1.w_off; p.bias1 = ctx->blob + l1.b_off;
+    ConvParams p = conv_params(image, (const float*)(wts.f16 + l2.w16_off), wts.f32 + l2.b_off, out, B, H, W, H, W, l2.cin_pad16 / 2, 3, 64, 64, 64, 1, 1, 1);
+    p.wpk1 = wts.f32 + l1.w_off; p.bias1 = wts.f32 + l1.b_off;
     p.im2col = 1; p.f16 = 1;
     const double px = (double)B * H * W;
     const double flops = 2.0 * 9 * (3.0 * 64 + 64.0 * 64) * px;
@@ -1105,7 +1107,7 @@ int run_trunk(hp3d_ctx* ctx, const char* scope, const float* image, int B, int H
     char nm2[64];
     snprintf(nm2, sizeof nm2, "%s/conv1_2", scope);
     int first = 1, fh = 0, fw = 0;
-    const int fused = f16 ? run_fused12(ctx, CL(ctx, nm), CL(ctx, nm2), image, B, ih, iw, a, &fh, &fw) : 0;
+    const int fused = f16 ? run_fused12(ctx, ConvW{ctx->blob, ctx->blob16, nullptr}, f16, CL(ctx, nm), CL(ctx, nm2), image, B, ih, iw, a, &fh, &fw) : 0;
     if (fused < 0) return fused;
     if (fused) { first = 2; ih = fh; iw = fw; }
     else CHK(run_conv(ctx, CL(ctx, nm), image, 3, B, ih, iw, a, 64, 0, nullptr, nullptr, f16));   // im2col fused in the loader
@@ -3753,6 +3755,106 @@ int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, con
     CHK(run_conv(ctx, ConvW{d_pk, nullptr, d_w}, l, d_x, in_cs, B, H, W, d_out, Cout, pool, nullptr, nullptr));
     HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
+}
+
+// The half-precision per-op entry points hand float32 back: a device result [n, cs] of halves (or float32: an out_f32 head) comes to
+// the host whole and its channels 0 .. C-1 are widened there (exact).  Ends the call like finish_op.
+static int finish_op_f16(hp3d_ctx* ctx, const void* d_out, size_t n, int cs, int C, int is_f32, float* out) {
+    std::vector<char> host(n * cs * (is_f32 ? 4 : 2));
+    HIPCHK(ctx, hipMemcpyAsync(host.data(), d_out, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+    CHK(finish_op(ctx));
+    const float* hf = (const float*)host.data();
+    const hp3d_f16* hh = (const hp3d_f16*)host.data();
+    for (size_t i = 0; i < n; ++i)
+        for (int c = 0; c < C; ++c) out[i * C + c] = is_f32 ? hf[i * cs + c] : (float)hh[i * cs + c];
+    return 0;
+}
+
+// One layer of a half-precision trunk ("op/conv2d_f16"): built and run like hp3d_conv2d's, through run_conv(f16 = 1).  The layer is
+// a plain one (mode 0) or the networks' first (mode 1: the raw float32 image); the concat permutation of mode 2 is a network matter.
+int hp3d_conv2d_f16(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin, const float* w_hwio, const float* bias,
+                    int k, int stride, int Cout, int act, int pool, int out_f32, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!x || !w_hwio || !bias || !out || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || k < 1 || stride < 1 || (long)B * H * W > 0x7fffffffL)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->profiling != 2) prof_reset(ctx);
+    ConvL l;
+    l.name = "op/conv2d_f16";
+    l.k = k; l.cin = Cin; l.cout = Cout; l.stride = stride; l.relu = act; l.net = 0;
+    l.mode = k == 3 && stride == 1 && Cin == 3 && Cout == 64 && !pool && !out_f32;       // the conv1_1 shape, as Tables::add_conv lays it out
+    l.ek = l.mode ? 1 : k; l.cin_pad = pad32(Cin); l.cout_pad = pad32(Cout);
+    size_t floats = 0, halves = 0;
+    reserve_conv(l, SEC_F16, floats, halves);
+    std::vector<float> packed(floats, 0.f);
+    pack_layer(l, w_hwio, bias, packed.data());            // the bias and conv1_1's im2col filter
+    std::vector<hp3d_f16> packed16(halves);
+    pack_conv16(l, w_hwio, packed16.data());
+    const size_t npix = (size_t)B * H * W;
+    Scratch S(ctx);
+    float* d_pk = S.upload(packed.data(), packed.size()); NN(ctx, d_pk);
+    hp3d_f16* d_pk16 = S.upload(packed16.data(), packed16.size()); NN(ctx, d_pk16);
+    float* d_x = S.upload(x, npix * Cin); NN(ctx, d_x);
+    const float* d_in = d_x;
+    int in_cs = Cin;
+    if (!l.mode) {         // what a trunk layer is fed: halves, channel stride cin_pad16, zero padding
+        hp3d_f16* d_x16 = S.alloc<hp3d_f16>(npix * l.cin_pad16); NN(ctx, d_x16);
+        HIPCHK(ctx, hipMemsetAsync(d_x16, 0, npix * l.cin_pad16 * sizeof(hp3d_f16), ctx->stream));
+        cvt_channels_f16_launch(d_x, (int)npix, Cin, Cin, d_x16, l.cin_pad16, ctx->stream);
+        d_in = (const float*)d_x16; in_cs = l.cin_pad16;
+    }
+    int Ho, Wo, pad;
+    same_pad(H, l.ek, stride, &Ho, &pad);
+    same_pad(W, l.ek, stride, &Wo, &pad);
+    const size_t opix = (size_t)B * (pool ? Ho / 2 : Ho) * (pool ? Wo / 2 : Wo);
+    const int out_cs = l.cout_pad;
+    const size_t obytes = opix * out_cs * (out_f32 ? 4 : 2);
+    char* d_out = S.alloc<char>(obytes); NN(ctx, d_out);
+    HIPCHK(ctx, hipMemsetAsync(d_out, 0xff, obytes, ctx->stream));        // (an output no kernel stores comes back as NaN)
+    CHK(run_conv(ctx, ConvW{d_pk, d_pk16, nullptr}, l, d_in, in_cs, B, H, W, (float*)d_out, out_cs, pool, nullptr, nullptr, 1, out_f32));
+    return finish_op_f16(ctx, d_out, opix, out_cs, Cout, out_f32, out);
+}
+
+// The first block of a half-precision trunk (conv1_1 + conv1_2 + 2x2 max-pool) as run_trunk runs it: the fused launch where option
+// "f16_fuse12" and the shape allow, else conv1_1 and the pooled conv1_2 one by one.
+int hp3d_first_block_f16(hp3d_ctx* ctx, const float* image, int B, int H, int W, const float* w1, const float* b1, const float* w2,
+                         const float* b2, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!image || !w1 || !b1 || !w2 || !b2 || !out || B < 1 || H < 2 || W < 2 || (long)B * H * W > 0x7fffffffL) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->profiling != 2) prof_reset(ctx);
+    ConvL l1, l2;
+    l1.name = "op/first_block_f16/conv1_1"; l2.name = "op/first_block_f16/conv1_2";
+    l1.k = l2.k = 3; l1.cin = 3; l2.cin = 64; l1.cout = l2.cout = 64; l1.stride = l2.stride = 1; l1.relu = l2.relu = 1; l1.net = l2.net = 0;
+    l1.mode = 1; l1.ek = 1; l1.cin_pad = 32; l1.cout_pad = 64;
+    l2.mode = 0; l2.ek = 3; l2.cin_pad = 64; l2.cout_pad = 64;
+    size_t floats = 0, halves = 0;
+    reserve_conv(l1, SEC_F16, floats, halves);
+    reserve_conv(l2, SEC_F16, floats, halves);
+    std::vector<float> packed(floats, 0.f);
+    std::vector<hp3d_f16> packed16(halves);
+    pack_layer(l1, w1, b1, packed.data());
+    pack_layer(l2, w2, b2, packed.data());
+    pack_conv16(l1, w1, packed16.data());
+    pack_conv16(l2, w2, packed16.data());
+    const size_t npix = (size_t)B * H * W, opix = (size_t)B * (H / 2) * (W / 2);
+    Scratch S(ctx);
+    float* d_pk = S.upload(packed.data(), packed.size()); NN(ctx, d_pk);
+    hp3d_f16* d_pk16 = S.upload(packed16.data(), packed16.size()); NN(ctx, d_pk16);
+    float* d_img = S.upload(image, npix * 3); NN(ctx, d_img);
+    hp3d_f16* d_out = S.alloc<hp3d_f16>(opix * 64); NN(ctx, d_out);
+    HIPCHK(ctx, hipMemsetAsync(d_out, 0xff, opix * 64 * sizeof(hp3d_f16), ctx->stream));
+    const ConvW wts{d_pk, d_pk16, nullptr};
+    int oh = 0, ow = 0;
+    const int fused = run_fused12(ctx, wts, 1, l1, l2, d_img, B, H, W, (float*)d_out, &oh, &ow);
+    if (fused < 0) return fused;
+    if (!fused) {
+        hp3d_f16* d_a = S.alloc<hp3d_f16>(npix * 64); NN(ctx, d_a);
+        HIPCHK(ctx, hipMemsetAsync(d_a, 0xff, npix * 64 * sizeof(hp3d_f16), ctx->stream));
+        CHK(run_conv(ctx, wts, l1, d_img, 3, B, H, W, (float*)d_a, 64, 0, nullptr, nullptr, 1));
+        CHK(run_conv(ctx, wts, l2, (const float*)d_a, 64, B, H, W, (float*)d_out, 64, 1, &oh, &ow, 1));
+    }
+    return finish_op_f16(ctx, d_out, opix, 64, 64, 0, out);
 }
 
 int hp3d_maxpool2(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C, float* out) {

@@ -516,6 +516,22 @@ int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double
  *                      sums of channel splits and tail pieces live in the context's scratch (grown on demand, kept until
  *                      hp3d_destroy), and with profiling on the call records its launches as rows named "op/conv2d"
  *                      (stage 1 of hp3d_get_timing).
+ * hp3d_conv2d_f16      one layer of a half-precision trunk ("op/conv2d_f16"): hp3d_conv2d's construction with the executor's
+ *                      dispatch in half precision, on a context of either precision, with or without finalized weights.
+ *                      x and the result are float32 on the host.  The conv1_1 shape (k = 3, stride 1, 3 -> 64, no pool) is fed
+ *                      the raw float32 image as in the networks; any other layer's input is rounded to half on the device
+ *                      (round to nearest even) into a buffer of channel stride ceil(Cin / 64) * 64 with zero padding, its filters
+ *                      are rounded to half on the host, the bias stays float32.  Sums are float32; the result is rounded to
+ *                      half and widened for the caller (exact), or stays float32 with out_f32 = 1 (the score-map heads).
+ *                      Kernel choice is the networks': options "f16_impl" ("h16": conv_h16.hip only where the launch fills the
+ *                      chip, "h16_force": wherever the shape allows, "mfma") and "f16_k7k1"; no cost model is asked.  The call moves
+ *                      "conv_h16_launches", "conv_mfma_launches", "conv_first_launches" and "conv_splitk_reduce_launches";
+ *                      a shape no half-precision kernel takes (stride 2, a pooled 7x7 ...) -> HP3D_ERR_UNSUPPORTED.
+ * hp3d_first_block_f16 the first block of a half-precision trunk, conv1_1 (3 -> 64) + conv1_2 (64 -> 64) + 2x2 max-pool, both
+ *                      leaky-ReLU: image [B,H,W,3] float32, w1 [3,3,3,64], w2 [3,3,64,64] HWIO -> out [B,H/2,W/2,64] (halves,
+ *                      widened).  One fused launch where option "f16_fuse12" ("1" | "ring" | "resident"), "f16_impl" and the
+ *                      shape (even H and W) allow ("conv_h16_first_resident_launches" tells the resident form), else conv1_1
+ *                      on conv_first.hip and the pooled conv1_2 through the dispatch above -- what the trunks do.
  * hp3d_maxpool2        NetworkOps.max_pool, 2x2/2 VALID                       utils/general.py:61-65
  * hp3d_avgpool8        tf.nn.avg_pool 8x8/8                                   nets/PosePriorNetwork.py:61
  * hp3d_resize_bilinear tf.image.resize_images (TF1.3 legacy bilinear)         nets/ColorHandPose3DNetwork.py:97,128,166
@@ -540,6 +556,11 @@ int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double
 int hp3d_conv2d(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin,
                 const float* w_hwio, const float* bias, int k, int stride, int Cout,
                 int act, int pool, float* out);
+int hp3d_conv2d_f16(hp3d_ctx* ctx, const float* x, int B, int H, int W, int Cin,
+                    const float* w_hwio, const float* bias, int k, int stride, int Cout,
+                    int act, int pool, int out_f32, float* out);
+int hp3d_first_block_f16(hp3d_ctx* ctx, const float* image, int B, int H, int W, const float* w1, const float* b1,
+                         const float* w2, const float* b2, float* out);
 int hp3d_maxpool2(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C, float* out);
 int hp3d_avgpool8(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C, float* out);
 int hp3d_resize_bilinear(hp3d_ctx* ctx, const float* x, int B, int H, int W, int C,
@@ -595,7 +616,7 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
- * "conv_splitk_reduce_launches" = channel-split reduces behind a conv_mfma / Winograd launch (whole path and hp3d_conv2d);
+ * "conv_splitk_reduce_launches" = channel-split reduces behind a conv_mfma / Winograd launch (whole path, hp3d_conv2d and hp3d_conv2d_f16);
  * "lift_overlap_calls" = lifting stages that ran their two towers on two streams (option "lift_overlap");
  * "lift_fused_launches" = lifting stages that ran as the one fused launch (option "lift_fused"); "comm_ranks" = ranks of the live RCCL communicator as RCCL itself
  * reports them (ncclCommCount), 0 without one -- bench.py prints it so that a multi-GPU line proves its own world size.

@@ -8,6 +8,11 @@ exact_data    small-integer inputs, weights that are multiples of the common den
               below 2^24 (scaled by that grid) float32 holds all of them exactly and the result must equal the reference BIT FOR BIT,
               whatever the tiling, channel split or summation order.
 rho           max |y - r| / (u abs_bound), u = 2^-24: the error of a non-exact run in units of the rounding of its partial sums.
+conv_ref_f16  the same layer in the half-precision trunks' arithmetic: operands rounded to half (nearest even), float64 sums, the
+              result rounded to half (unless out_f32); first_block_ref_f16 chains conv1_1 and the pooled conv1_2.
+exact_data_f16  integer data on which a half-precision layer must equal conv_ref_f16 bit for bit: partial sums below 2^24 and
+              pre-activations within +-1024, where every integer y and every half(0.01f y) is its own half (neg_slope_halves_distinct).
+gate_f16      the tolerance of a half-precision run on non-integer data: half a half-spacing + the float32 sums' rho gate.
 
 The transform matrices restate the kernels': F(2x2,3x3) conv_wino.hip / conv_wino2.hip (B^T at the input transform, A^T in the
 epilogue, G in wino_pack_weights); F(4x4,3x3) wino4_shared.h (w4_bt_t, w4_at_t) and wino4_pack_weights / wino4s_pack_weights; F(4x4,4x4)
@@ -349,3 +354,131 @@ def wino_f32(x, w, b, kind, act=True, pieces=None, u_scale=None, track=None):
         track.append(np.repeat(np.repeat(big, m, 1), m, 2)[:, :H, :W])
     y = (Y + np.asarray(b, np.float32)).astype(np.float32)
     return np.maximum(y, LEAKY * y) if act else y
+
+
+# --------------------------------------------------------------------------- half precision (conv_h16.hip, the F16 forms of conv_mfma.hip / conv_first.hip)
+U16 = 2.0 ** -11                       # unit roundoff of half
+HALF_EXACT_MAX = 1024                  # |pre-activation| of an exact half-precision run (every integer up to 2048 is a half)
+
+
+def _h(a):
+    """Round to half, to nearest even (what cvt_channels_f16_kernel, pack_conv16 and the epilogues' (hp3d_f16) casts do), as float64."""
+    return np.asarray(a).astype(np.float16).astype(np.float64)
+
+
+def pre_f16(x, w, b, stride=1):
+    """float64 pre-activation of a half-precision layer: half(x) * half(w) summed in float64, + the float32 bias."""
+    with torch.no_grad():
+        return (_conv64(_t(_h(x)), _t(_h(w)), stride) + _t(b)).numpy()
+
+
+def conv_ref_f16(x, w, b, stride=1, act=True, pool=False, out_f32=False, first=False, pre=None):
+    """float64-valued NHWC reference of hp3d_conv2d_f16: pre_f16, the activation as conv_ref_f64 applies it (the kernels' float32
+    max(v, 0.01f v) on float32(v) wherever the pre-activation is a float32 value -- an exact run --, in float64 elsewhere), ONE rounding
+    to half (nearest even, sub-normals kept) unless out_f32, then the 2x2 max-pool (rounding is monotone: the kernels that pool
+    before they round give the same).  first: the layer is conv1_1 (raw float32 image, 3 -> 64, k = 3) -- the same arithmetic here; the
+    kernel's own extra rounding of that layer (its bias rides through the half MFMA) is gate_f16's term, not the reference's.
+    pre: pre_f16(x, w, b, stride) if the caller has it."""
+    if first:
+        assert w.shape == (3, 3, 3, 64) and stride == 1 and not out_f32
+    r = pre_f16(x, w, b, stride) if pre is None else pre
+    if act:
+        r32 = r.astype(np.float32)
+        if np.array_equal(r32.astype(np.float64), r):
+            r = np.maximum(r32, LEAKY * r32).astype(np.float64)
+        else:
+            r = np.maximum(r, np.float64(LEAKY) * r)
+    if not out_f32:
+        r = _h(r)
+    return _pool2(r) if pool else r
+
+
+def first_block_ref_f16(image, w1, b1, w2, b2):
+    """conv1_1 + conv1_2 + 2x2 max-pool of a half-precision trunk: conv1_1's half output is conv1_2's input, and conv1_2's SAME
+    padding pads that OUTPUT with zeros.  Returns (reference [B, H/2, W/2, 64], conv1_1's output)."""
+    y1 = conv_ref_f16(image, w1, b1, first=True)
+    return conv_ref_f16(y1, w2, b2, pool=True), y1
+
+
+def neg_slope_halves_distinct(lo=-1600):
+    """half(0.01f y), y = lo .. 0 as the kernels form it (float32 product, then nearest-even half): True if pairwise distinct."""
+    y = np.arange(lo, 1, dtype=np.float32)
+    h = (LEAKY * y).astype(np.float16)
+    return len(np.unique(h.view(np.uint16))) == len(y)
+
+
+def exact_data_f16(shape, rng, density=1.0, xmax=2, bmax=8):
+    """Integer x in {-xmax .. xmax}, w in {-1, 0, 1} with a fraction `density` non-zero, integer b in {-bmax .. bmax} (float32
+    arrays) for shape (B, H, W, Cin, Cout, k).  Returns (x, w, b, bound), bound = abs_bound('direct').  The caller asserts
+    exact_ok_f16 on it: data are not thinned here to meet it."""
+    B, H, W, Cin, Cout, k = shape
+    x = rng.integers(-xmax, xmax + 1, (B, H, W, Cin)).astype(np.float32)
+    w = np.where(rng.random((k, k, Cin, Cout)) < density, rng.choice([-1.0, 1.0], (k, k, Cin, Cout)), 0.0).astype(np.float32)
+    b = rng.integers(-bmax, bmax + 1, Cout).astype(np.float32)
+    return x, w, b, abs_bound(x, w, 'direct', b)
+
+
+def first_block_data_f16(shape, rng, density2=0.125):
+    """(B, H, W): image in {0, 1}, w1 dense in {-1, 0, 1}, b1 = 27 (conv1_1's output is then an integer in 0 .. 54 and its
+    leaky-ReLU the identity), w2 in {-1, 0, 1} at `density2`, integer b2 in {-8 .. 8}."""
+    B, H, W = shape
+    image = rng.integers(0, 2, (B, H, W, 3)).astype(np.float32)
+    w1 = rng.choice([-1.0, 0.0, 1.0], (3, 3, 3, 64)).astype(np.float32)
+    b1 = np.full(64, 27, np.float32)
+    w2 = np.where(rng.random((3, 3, 64, 64)) < density2, rng.choice([-1.0, 1.0], (3, 3, 64, 64)), 0.0).astype(np.float32)
+    b2 = rng.integers(-8, 9, 64).astype(np.float32)
+    return image, w1, b1, w2, b2
+
+
+def exact_ok_f16(bound, pre):
+    """The preconditions of an exact half-precision run: (a) every partial sum below 2^24 (float32 holds it), (b) every
+    pre-activation an integer within +-HALF_EXACT_MAX -- y >= 0 is then its own half and half(0.01f y) tells any two y < 0 apart
+    (neg_slope_halves_distinct), so a sum that is off by one changes the stored half."""
+    return bool(float(np.max(bound)) < 2.0 ** 24 and float(np.max(np.abs(pre))) <= HALF_EXACT_MAX and np.array_equal(pre, np.round(pre)))
+
+
+def spacing_half(v):
+    """Distance between neighbouring halves at |v| (2^-24 in the sub-normal range)."""
+    e = np.floor(np.log2(np.maximum(np.abs(np.asarray(v, np.float64)), 2.0 ** -14)))
+    return 2.0 ** (e - 10)
+
+
+def first_bias_term(b):
+    """conv_first_kernel<true> / the fused forms' patch stage carry conv1_1's float32 bias through the half MFMA as two rows, hi =
+    half(b) and half(b - hi) (operand 1.0 each).  b - hi is exact in float32 and at most 2^-11 |b|; its own rounding to half errs by
+    at most 2^-11 of that, or by half a sub-normal spacing where it falls below 2^-14: 2^-22 |b| + 2^-25 per output channel."""
+    return 2.0 ** -22 * np.abs(np.asarray(b, np.float64)) + 2.0 ** -25
+
+
+def gate_f16(y, r, bound, cin, k, out_f32=False, first_b=None):
+    """Per-output tolerance of a half-precision run y against r = conv_ref_f16(..., out_f32=True) (the UNROUNDED reference; pooled
+    like y, `bound` through pool_bound):  1/2 spacing_half(max(|y|, |r|))   the one nearest-even rounding of the stored half
+                                          + rho_gate('direct') u32 bound     the float32 sums of exact half products
+                                          (+ first_bias_term(first_b))       conv1_1 on conv_first.hip.
+    A truncating epilogue errs by up to a whole spacing, flushed sub-normals by up to 2^-14 against a spacing of 2^-24."""
+    tol = rho_gate('direct', cin, k) * U32 * np.asarray(bound, np.float64)
+    if not out_f32:
+        tol = tol + 0.5 * spacing_half(np.maximum(np.abs(np.asarray(y, np.float64)), np.abs(r)))
+    if first_b is not None:
+        tol = tol + first_bias_term(first_b)
+    return tol
+
+
+def rho_f16(y, r, bound, out_f32=False, first_b=None):
+    """The measured rho of a half-precision run: what is left of |y - r| after the half rounding's (and conv1_1's bias rows') share,
+    in units of u32 bound."""
+    err = np.abs(np.asarray(y, np.float64) - r)
+    if not out_f32:
+        err = err - 0.5 * spacing_half(np.maximum(np.abs(np.asarray(y, np.float64)), np.abs(r)))
+    if first_b is not None:
+        err = err - first_bias_term(first_b)
+    return float(np.max(np.maximum(err, 0.0) / (U32 * np.maximum(bound, 1e-300))))
+
+
+def half_trunc(v):
+    """v rounded to half TOWARDS ZERO (the wrong rounding mode the checks must see), as float64."""
+    v = np.asarray(v, np.float64)
+    h = v.astype(np.float16)
+    over = np.abs(h.astype(np.float64)) > np.abs(v)
+    h[over] = np.nextafter(h[over], np.float16(0))
+    return h.astype(np.float64)
