@@ -18,8 +18,9 @@
 //     inline-asm statement that holds a plane's eight MFMAs (left alone, hipcc moved ~10 tuples per step between the files);
 //   * V = B^T d B double buffered in LDS: 2 x 36 planes x 32 tiles x 16 channels = 147 KB;
 //   * loader thread = (tile, channel pair): 36 window loads of 8 bytes; the offsets are 6 row + 6 column terms (a row /
-//     column outside the image carries a constant that pushes the sum out of the buffer's range: reads as 0) added at
-//     issue time, not 36 registers; the loads are spread two per plane over the first 18 planes of a step, in CLASS order: the
+//     column outside the image carries a constant that pushes the sum out of the buffer's range: reads as 0), not 36
+//     registers -- added once per step where the width is ragged, and for widths that are a multiple of 4 (3x3) not added at all:
+//     row offsets per column class + the column in the load's scalar offset (COLCLS, below); the loads are spread two per plane over the first 18 planes of a step, in CLASS order: the
 //     elements (r, c), (r + 4, c), (r, c + 4), (r + 4, c + 4) -- the same pixels seen from neighbouring tiles -- follow each other, so
 //     the repeats hit the L1 line or its pending fill (round 4: +2.7 %);
 //   * a 3x3 plane is FOUR statements of two MFMAs with one of the plane's memory instructions behind each (next plane's A fragments |
@@ -37,6 +38,15 @@
 #include <type_traits>
 
 #define W4_WLOAD HP3D_BUFFER_LOAD8
+// LDS accesses of the step loop through 32-bit addresses that already CONTAIN the address of V (W4_LDS_ADDR, added once outside the loop): formed as
+// V + offset inside the loop, every per-step base cost one more VALU instruction for the symbol's (link-time) address.  The interpreter keeps offsets.
+#ifdef HP3D_EMU
+#define W4_LDS_ADDR(V) 0
+#define W4_LDS_AT(T, V, addr) ((T*)((char*)(V) + (addr)))
+#else
+#define W4_LDS_ADDR(V) ((int)(unsigned)(size_t)(__attribute__((address_space(3))) void*)(V))
+#define W4_LDS_AT(T, V, addr) ((__attribute__((address_space(3))) T*)(size_t)(unsigned)(addr))
+#endif
 // -DHP3D_W4_TIMING=1: diagnostic build -- every wave sums shader-clock intervals of its steps into w4_timing[] and conv_wino4_launch prints
 // them (wino4_diag.h; profiles/r04_tuning_notes.md section 4).  The shipped build sees empty macros.  (Round 4's timing ABLATIONS -- builds
 // that compute wrong results on purpose, HP3D_W4_ABL -- were removed from this file in round 5: all settled, recorded in r03 / r04_tuning_notes.md.)
@@ -79,11 +89,15 @@ constexpr int W4_PIECE_FLOATS = W4_TILES * 16 * W4_COUTS;       // raw 4x4 outpu
 // workgroup.  A run lies in one item or crosses into the next: at most two PIECES per workgroup, whose raw sums (the output
 // transform is linear) go to a compact scratch [workgroup][piece 2][tile][pixel][cout]; wino4_tail_reduce adds an item's pieces in
 // step order, + bias, activation (+ pool), and stores.  Deterministic; only the summation order of the tail items changes.
-template <bool POOL, int NSUB, bool SPLITK, bool TAIL>
+// RAGGED (3x3 only; the launcher's choice, once per launch): false = the image width is a multiple of 4 and the window loads take their
+// column from the scalar offset (COLCLS below); true = any width, row + column terms added per step.
+template <bool POOL, int NSUB, bool SPLITK, bool TAIL, bool RAGGED>
 HP3D_KERNEL2(256, 1)
 void conv_wino4_kernel(const ConvParams p) {
     static_assert(!(POOL && SPLITK), "the fused max-pool needs complete sums");
     static_assert(!(TAIL && (SPLITK || NSUB != 1)), "tail pieces: plain 3x3 launches only");
+    static_assert(NSUB == 1 || RAGGED, "the nine-block form keeps the row + column terms (one instantiation)");
+    constexpr bool COLCLS = NSUB == 1 && !RAGGED;
     constexpr bool VARSTEPS = SPLITK || TAIL;         // items own a RANGE of the channel steps
     HP3D_DYN_SMEM(V);
     int* tinfo = (int*)(V + 2 * W4_VBUF_FLOATS);       // [parity][0..31] output offset of tile t (-1: none), [32..63] edge flags
@@ -127,19 +141,52 @@ void conv_wino4_kernel(const ConvParams p) {
     // ---- loader role: this thread transforms the 6x6 window of tile lt for channel pair lp ------------------------------
     const int lt = tid >> 3, lp = tid & 7;
     const int cs4 = p.in_cs * 4;
+    const hp3d_rsrc_t irsrc = HP3D_MAKE_RSRC(p.in, (unsigned)p.B * (unsigned)(p.H * p.W) * (unsigned)cs4);
     constexpr int OOR = (int)0x80000000;          // row outside the image / no such tile
     constexpr int COL_OOR = 0x60000000;           // column outside the image: any row term + this is >= 2^30 > the buffer's extent
-    int ro[6], co[6];
+    // COLCLS: W % 4 == 0, so window columns 1..4 of every tile lie inside the image, column 0 is outside for the leftmost tile column only and
+    // column 5 for the rightmost only.  The row offsets then exist once per COLUMN CLASS, made once per item: ro[r] = the address of (row r,
+    // column 0), ro[6 + r] of (r, column 1), ro[12 + r] of (r, column 5), each out of the buffer's range where the row, the tile or that class's
+    // column is outside.  The two border classes are the middle one + a per-lane distance (wdl = -cs4, wdr = 4 cs4, or COL_OOR where the tile has no
+    // such column): across an item's epilogue only the middle class and the two distances stay live, the border classes are formed again behind it
+    // (window_classes: 12 additions per item) -- eighteen registers held across the epilogue came back from scratch between its stores.
+    // A load of element (r, c) takes the class's register as it stands and the rest of the column, (c - 1) * cs4 for c = 1..4, in its SCALAR
+    // offset: no vector arithmetic per step.  (Every class is based on a pixel of its own because the buffer's range check sees the vector
+    // offset alone: based on column 0, the top-left tile of image 0 would present a negative vector offset for its in-range columns.)
+    int ro[COLCLS ? 18 : 6], co[6];
+    [[maybe_unused]] int wdl = 0, wdr = 0;
+    auto wcls = [](int c) { return c == 0 ? 0 : c == 5 ? 2 : 1; };        // column -> class, and the columns left to the scalar offset
+    auto wcol = [](int c) { return (c == 0 || c == 5) ? 0 : c - 1; };
     int cb = 0, cty = 0, ctx_ = 0;                // NSUB = 9 only: tile coordinates stay live for the block shifts
+    // (an address inside the buffer is below 2^30: + COL_OOR it lies in [2^30, 2^31); OOR + COL_OOR, OOR - cs4 and OOR + 4 cs4 stay above 2^30 as well)
+    auto window_classes = [&]() {
+        if constexpr (COLCLS) {
+#pragma unroll
+            for (int r = 0; r < 6; ++r) { ro[r] = (int)((unsigned)ro[6 + r] + (unsigned)wdl); ro[12 + r] = (int)((unsigned)ro[6 + r] + (unsigned)wdr); }
+        }
+    };
     auto window_offsets = [&](bool valid, int lb, int lty, int ltx, int sub) {
         const int dy = NSUB == 1 ? 0 : 3 * (sub / 3) - 2, dx = NSUB == 1 ? 0 : 3 * (sub % 3) - 2;
         const int wy0 = 4 * lty - 1 + dy, wx0 = 4 * ltx - 1 + dx;
         const int wbase = ((lb * p.H + wy0) * p.W + wx0) * cs4 + lp * 8;
         const bool tv = valid && lb < p.B;
+        if constexpr (COLCLS) {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) ro[r] = (tv && (unsigned)(wy0 + r) < (unsigned)p.H) ? wbase + r * (p.W * cs4) : OOR;
+            for (int r = 0; r < 6; ++r) ro[6 + r] = (tv && (unsigned)(wy0 + r) < (unsigned)p.H) ? wbase + cs4 + r * (p.W * cs4) : OOR;
+            wdl = wx0 >= 0 ? -cs4 : COL_OOR;
+            wdr = wx0 + 5 < p.W ? 4 * cs4 : COL_OOR;
+            window_classes();
+        } else {
 #pragma unroll
-        for (int c = 0; c < 6; ++c) co[c] = (unsigned)(wx0 + c) < (unsigned)p.W ? c * cs4 : COL_OOR;
+            for (int r = 0; r < 6; ++r) ro[r] = (tv && (unsigned)(wy0 + r) < (unsigned)p.H) ? wbase + r * (p.W * cs4) : OOR;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) co[c] = (unsigned)(wx0 + c) < (unsigned)p.W ? c * cs4 : COL_OOR;
+        }
+    };
+    // window element e = (r, c) of the step whose channel offset is soff
+    auto window_load = [&](int e, int soff) {
+        if constexpr (COLCLS) return W4_WLOAD(irsrc, ro[wcls(e % 6) * 6 + e / 6], soff + wcol(e % 6) * cs4);
+        else return W4_WLOAD(irsrc, (int)((unsigned)ro[e / 6] + (unsigned)co[e % 6]), soff);
     };
     auto loader_setup = [&](int tblock, bool valid, int sub) {
         int lb, lty, ltx;
@@ -148,13 +195,12 @@ void conv_wino4_kernel(const ConvParams p) {
         window_offsets(valid, lb, lty, ltx, NSUB > 1 ? sub : 0);
     };
     auto loader_shift = [&](int sub) { window_offsets(true, cb, cty, ctx_, sub); };
-    const hp3d_rsrc_t irsrc = HP3D_MAKE_RSRC(p.in, (unsigned)p.B * (unsigned)(p.H * p.W) * (unsigned)cs4);
     [[maybe_unused]] const unsigned out_bytes = (unsigned)(SPLITK ? p.ksplit * p.B : p.B) * (unsigned)(Hs * Ws) * (unsigned)p.out_cs * 4u;
 
     f32x2 d[36];
     auto window_fetch = [&](int soff) {
 #pragma unroll
-        for (int e = 0; e < 36; ++e) d[e] = W4_WLOAD(irsrc, (int)((unsigned)ro[e / 6] + (unsigned)co[e % 6]), soff);
+        for (int e = 0; e < 36; ++e) d[e] = window_load(e, soff);
     };
     float* const Vw = V + lt * W4_CK + ((lp >> 1) ^ w4_swz(lt)) * 4 + (lp & 1) * 2;      // this thread's slot in plane 0 of buffer 0
     // B^T d B in place: along the window rows first (plane row a), then along the columns (plane column b); afterwards d[a * 6 + b] is this
@@ -171,6 +217,12 @@ void conv_wino4_kernel(const ConvParams p) {
         float* Vq0 = Vw + buf * W4_VBUF_FLOATS;
         float* dst = pl < W4_HALF ? Vq0 + pl * W4_PLANE_FLOATS : Vq0 + W4_HALF * W4_PLANE_FLOATS + (pl - W4_HALF) * W4_PLANE_FLOATS;
         *(f32x2*)dst = d[pl];
+    };
+    // the same store from two byte offsets made once per step (3x3): planes 0..17 from vw0, 18..35 from vw1, every plane inside the 16-bit immediate
+    // (from one base the planes 32..35 lie past 64 KB and took an address instruction each, alone between MFMA pairs)
+    const int vw_lane = W4_LDS_ADDR(V) + (lt * W4_CK + ((lp >> 1) ^ w4_swz(lt)) * 4 + (lp & 1) * 2) * 4;
+    auto v_write2 = [&](int vw0, int vw1, int pl) {
+        *W4_LDS_AT(f32x2, V, (pl < W4_HALF ? vw0 : vw1) + (pl < W4_HALF ? pl : pl - W4_HALF) * (W4_PLANE_FLOATS * 4)) = d[pl];
     };
     auto transform_commit = [&](int buf) {
         transform_arith();
@@ -192,14 +244,20 @@ void conv_wino4_kernel(const ConvParams p) {
 
     f32x4 M[W4_NP][2];     // [plane][tile half]: rows = tiles 16 m + 4 (lane >> 4) + r, column = cout (lane & 15)
     f32x4 bq[W4_RING];
-    auto b_fetch = [&](int slot, int voff, int soff) { bq[slot] = HP3D_BUFFER_LOAD16(wrsrc, voff, soff); };
-    const int va_lane = (ln * W4_CK + ((lq ^ w4_swz(ln)) * 4)) * 4;
+    // 3x3: the lane's 16 bytes are the vector offset, the wave's fragment column (wvoff, uniform) rides in the scalar offset -- choosing between this
+    // item's and the next item's column is then a scalar select, not a v_cndmask per step.  (7x7: one vector offset, as before.)
+    const int wlane = lane * 16;
+    auto b_fetch = [&](int slot, int voff, int soff) {
+        if constexpr (NSUB == 1) bq[slot] = HP3D_BUFFER_LOAD16(wrsrc, wlane, voff + soff);
+        else bq[slot] = HP3D_BUFFER_LOAD16(wrsrc, voff, soff);
+    };
+    const int va_lane = W4_LDS_ADDR(V) + (ln * W4_CK + ((lq ^ w4_swz(ln)) * 4)) * 4;
     int ab0 = 0, ab1 = 0;
     f32x4 af[W4_ADEPTH][2];
     auto a_fetch = [&](int set, int plane) {
         const int base = plane < W4_HALF ? ab0 : ab1, pl = plane < W4_HALF ? plane : plane - W4_HALF;
 #pragma unroll
-        for (int m = 0; m < 2; ++m) af[set][m] = *(const f32x4*)((const char*)V + base + (pl * W4_PLANE_FLOATS + m * 16 * W4_CK) * 4);
+        for (int m = 0; m < 2; ++m) af[set][m] = *W4_LDS_AT(const f32x4, V, base + (pl * W4_PLANE_FLOATS + m * 16 * W4_CK) * 4);
     };
 
     // virtual item id -> cout block, tile block, channel steps [s0_, s1_), piece slot (-1 = a whole item / a slice of the [ksplit] scratch)
@@ -245,7 +303,7 @@ void conv_wino4_kernel(const ConvParams p) {
     int sub_cur = sub0;                           // block (i, j) = (sub_cur / 3, sub_cur % 3) of the 9x9 extension the current step belongs to
     loader_setup(tblock, true, sub0);
     table_write(tblock, 0, kz, piece);
-    int wvoff = (cy * (W4_COUTS / 16) + wave) * 1024 + lane * 16;
+    int wvoff = (cy * (W4_COUTS / 16) + wave) * 1024 + (NSUB == 1 ? 0 : wlane);
     window_fetch((s0 - sub0 * csteps) * (W4_CK * 4));
 #pragma unroll
     for (int t = 0; t < W4_RING; ++t) b_fetch(t, wvoff, soff_of(t, s0));
@@ -287,8 +345,10 @@ void conv_wino4_kernel(const ConvParams p) {
             // fragments anyway -- not one v_add_u32 in front of each load between the MFMA pairs: a float32 MFMA and a VALU instruction of the same
             // wave do not overlap, and a lone VALU result feeding a load address between MFMAs costs 15 ns in isolation (profiles/r06_tuning_notes.md
             // section 7; in situ the adds were worth 1.0-1.5 %).  An address lives in the register pair its load fills.
-            int wa[36];
-            if (NSUB == 1) {
+            // COLCLS (every width that is a multiple of 4) has no such block: its loads take a row register of their column class and a scalar offset.
+            [[maybe_unused]] int wa[36];
+            [[maybe_unused]] int vw0 = 0, vw1 = 0;
+            if constexpr (NSUB == 1 && !COLCLS) {
 #pragma unroll
                 for (int e = 0; e < 36; ++e) { wa[e] = (int)((unsigned)ro[e / 6] + (unsigned)co[e % 6]); HP3D_OPAQUE_V(wa[e]); }
             }
@@ -330,7 +390,7 @@ void conv_wino4_kernel(const ConvParams p) {
                             constexpr int PER = 36 / (2 * (W4_NP - 1 - W4_TRANSFORM_AT));
                             static_assert(PER * 2 * (W4_NP - 1 - W4_TRANSFORM_AT) == 36, "");
 #pragma unroll
-                            for (int j = 0; j < PER; ++j) v_write(cur ^ 1, ((pl - W4_TRANSFORM_AT - 1) * 2 + (e - 1)) * PER + j);
+                            for (int j = 0; j < PER; ++j) v_write2(vw0, vw1, ((pl - W4_TRANSFORM_AT - 1) * 2 + (e - 1)) * PER + j);
                         } else {
                             static_assert(W4_WPP % 2 == 0, "the plane's window loads go behind its two middle pairs, half each");
 #pragma unroll
@@ -338,7 +398,8 @@ void conv_wino4_kernel(const ConvParams p) {
                                 const int wk = pl * W4_WPP + (e - 1) * (W4_WPP / 2) + j;
                                 if (wk < 36) {
                                     const int we = W4_ISSUE_ELEM(wk < 36 ? wk : 0);
-                                    d[we] = W4_WLOAD(irsrc, wa[we], wsoff);
+                                    if constexpr (COLCLS) d[we] = window_load(we, wsoff);
+                                    else d[we] = W4_WLOAD(irsrc, wa[we], wsoff);
                                 }
                             }
                         }
@@ -377,6 +438,12 @@ void conv_wino4_kernel(const ConvParams p) {
                 if (pl == W4_TRANSFORM_AT) {
                     W4_T_WINDOW_WAIT(W4_TRANSFORM_AT + 1 - 36 / W4_WPP);      // (timing build: marks 0 and 5 around the wait for the window data)
                     transform_arith();
+                    if constexpr (NSUB == 1) {        // (inside the transform's block of VALU instructions)
+                        vw0 = (cur ^ 1) * (W4_VBUF_FLOATS * 4) + vw_lane;
+                        vw1 = vw0 + W4_HALF * W4_PLANE_FLOATS * 4;
+                        HP3D_OPAQUE_V(vw0);
+                        HP3D_OPAQUE_V(vw1);
+                    }
                     W4_T_MARK(1);
                 }
             }
@@ -393,7 +460,12 @@ void conv_wino4_kernel(const ConvParams p) {
             if (has_next) split_of(n_item, n_kz, n_cy, n_tblock, n_piece, n_s0, n_s1);
             if (VARSTEPS) { n_kz = HP3D_READFIRSTLANE(n_kz); n_cy = HP3D_READFIRSTLANE(n_cy); n_tblock = HP3D_READFIRSTLANE(n_tblock); n_piece = HP3D_READFIRSTLANE(n_piece);
                             n_s0 = HP3D_READFIRSTLANE(n_s0); n_s1 = HP3D_READFIRSTLANE(n_s1); }
-            n_wvoff = (n_cy * (W4_COUTS / 16) + wave) * 1024 + lane * 16;
+            n_wvoff = (n_cy * (W4_COUTS / 16) + wave) * 1024 + (NSUB == 1 ? 0 : wlane);
+        }
+        if constexpr (COLCLS) {       // the border classes of this item's windows, again (see ro[] above)
+            HP3D_OPAQUE_V(wdl);
+            HP3D_OPAQUE_V(wdr);
+            window_classes();
         }
         step_body(s0, std::true_type{});
         // (the tile table of the next item goes into the other parity only now: the barrier that ended the step above is what tells
@@ -581,10 +653,10 @@ int conv_wino4_tail_plan(int Cin, int Cout, int Ho, int Wo, int B, int* tail_ite
     return q;
 }
 
-template <bool POOL, int NSUB, bool SPLITK, bool TAIL>
+template <bool POOL, int NSUB, bool SPLITK, bool TAIL, bool RAGGED>
 static void wino4_launch_t(const ConvParams& p, long tiles, hipStream_t s) {
     static bool attr_done[64] = {};
-    auto k = conv_wino4_kernel<POOL, NSUB, SPLITK, TAIL>;
+    auto k = conv_wino4_kernel<POOL, NSUB, SPLITK, TAIL, RAGGED>;
     if (hp3d_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, W4_SMEM_BYTES);
     const long items = (tiles + W4_TILES - 1) / W4_TILES * (p.Cout / W4_COUTS) * (SPLITK ? p.ksplit : 1);
@@ -607,25 +679,30 @@ int conv_wino4_launch(const ConvParams& pin, int pool, hipStream_t s) {
     p.tiles_y = (p.Ho + 3) / 4;
     const long tiles = (long)p.B * p.tiles_x * p.tiles_y;
     if (pool && (p.nsub != 1 || ((p.Ho | p.Wo) & 1))) return -1;
+    // a width that is not a multiple of 4 (or, never the case for these SAME / stride-1 layers, an output width that is not the input's) keeps
+    // the row + column form of the window addresses: up to three right-hand window columns can then lie outside the image
+    const bool ragged = (p.W & 3) != 0 || p.W != p.Wo;
     if (p.ksplit > 1) {
         const int nsteps = p.nsub * p.Cin / W4_CK;
         if (pool || p.ksplit * 2 > nsteps || p.out_cs != p.Cout) return -1;
-        if (p.nsub == 9) wino4_launch_t<false, 9, true, false>(p, tiles, s); else wino4_launch_t<false, 1, true, false>(p, tiles, s);
+        if (p.nsub == 9) wino4_launch_t<false, 9, true, false, true>(p, tiles, s);
+        else if (ragged) wino4_launch_t<false, 1, true, false, true>(p, tiles, s);
+        else wino4_launch_t<false, 1, true, false, false>(p, tiles, s);
         W4_T_REPORT(p, s, p.nsub == 9 ? "7x7 split" : "3x3 split");
         return 0;
     }
     p.ksplit = 1;
     p.tail_items = p.tail_q = 0;
     if (p.nsub == 9) {
-        wino4_launch_t<false, 9, false, false>(p, tiles, s);
+        wino4_launch_t<false, 9, false, false, true>(p, tiles, s);
         W4_T_REPORT(p, s, "7x7");
         return 0;
     }
     // 3x3: the same instantiation serves launches with and without tail pieces (tail_items = 0: every item is a whole item)
     if (p.partial && p.partial_cap >= conv_wino4_tail_floats() && !(pool && (p.cout_store & 3)) && (p.out_cs & 3) == 0 && ((uintptr_t)p.out & 15) == 0)
         p.tail_q = conv_wino4_tail_plan(p.Cin, p.Cout, p.Ho, p.Wo, p.B, &p.tail_items);
-    if (pool) wino4_launch_t<true, 1, false, true>(p, tiles, s);
-    else wino4_launch_t<false, 1, false, true>(p, tiles, s);
+    if (pool) { if (ragged) wino4_launch_t<true, 1, false, true, true>(p, tiles, s); else wino4_launch_t<true, 1, false, true, false>(p, tiles, s); }
+    else { if (ragged) wino4_launch_t<false, 1, false, true, true>(p, tiles, s); else wino4_launch_t<false, 1, false, true, false>(p, tiles, s); }
     W4_T_REPORT(p, s, pool ? "3x3 pool" : "3x3");
     if (p.tail_items > 0) {
         const long total = (long)p.tail_items * W4_TILES * (pool ? 4 : 16) * (W4_COUTS / 4);
