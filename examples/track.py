@@ -8,6 +8,7 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py --synthetic                  (seeded synthetic weights + frames)
     python examples/track.py --synthetic --hands 2        (up to K hands per frame, each in its own slot: DESIGN.md 4.13)
     python examples/track.py video_hd.npy --detect-scale 4   (detect on the 4 x 4 area mean, crop from the frame: DESIGN.md 4.14)
+    python examples/track.py video_hd.npy --nv12             (the frames as NV12 planes, what a decoder delivers: DESIGN.md 4.17)
 """
 import glob
 import json
@@ -31,6 +32,11 @@ if __name__ == '__main__':
     ap.add_argument('--partial-detect', action='store_true',
                     help='a step that detects because some frames of a batch lost their hand runs HandSegNet on those frames only '
                          '(DESIGN.md 4.16; single-hand tracking)')
+    ap.add_argument('--nv12', action='store_true',
+                    help='convert the loaded frames to NV12 planes and track on those: crop and detection frame come straight from the '
+                         'planes (DESIGN.md 4.17; frames with even height and width)')
+    ap.add_argument('--nv12-matrix', default='bt709', choices=('bt709', 'bt601', 'bt709_full', 'bt601_full'),
+                    help='the colour matrix of --nv12, both ways (default bt709: HD video)')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -66,9 +72,17 @@ if __name__ == '__main__':
     net.track_hands_reset()
     if a.hands:
         hand_side_v = np.tile(hand_side_v, (1, a.hands, 1)).reshape(1, a.hands, 2)          # which slot holds a left hand is the caller's knowledge
+    if a.nv12:
+        from hand3d_amd.utils.nv12 import rgb_to_nv12
+        net.engine.set_option('nv12_matrix', a.nv12_matrix)
     for i, frame in enumerate(frames):
         frame = np.asarray(frame)
-        if frame.dtype == np.uint8:
+        if a.nv12:           # (a video source hands the planes over as they are; here they are made from the loaded frame)
+            if frame.dtype != np.uint8:
+                frame = (frame + 0.5) * 255.0 if a.float_range == 'normalised' else frame
+                frame = np.clip(np.floor(np.asarray(frame, np.float64) + 0.5), 0, 255).astype(np.uint8)
+            image_v = rgb_to_nv12(frame[None], a.nv12_matrix)
+        elif frame.dtype == np.uint8:
             image_v = frame[None]                      # tracked steps crop straight from the uint8 frame
         elif a.float_range == '255':
             image_v = frame[None].astype(np.float32) / 255.0 - 0.5

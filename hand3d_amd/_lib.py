@@ -77,6 +77,15 @@ _SIGNATURES = {
     'hp3d_track_seed': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'hp3d_track_step': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
     'hp3d_track_step_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    'hp3d_track_step_nv12': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 11),
+    'hp3d_track_step_nv12_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 11),
+    'hp3d_track_hands_step_nv12': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_track_hands_step_nv12_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_nv12_to_rgb': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    'hp3d_crop_and_resize_nv12': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_downscale_nv12': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_int, C.c_void_p]),
     'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
     'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
     'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -552,6 +561,92 @@ class Engine(object):
         v = lambda p: C.c_void_p(int(p)) if p else None
         self._chk(self.lib.hp3d_track_step_dev(self.h, B, H, W, v(image_ptr), v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap),
                                                v(coord3d), v(kp_crop), v(kp_hw), v(confidence), v(lost), v(detected)))
+
+    # -- NV12 frames (include/hp3d.h "NV12 frames") ------------------------------------
+    @staticmethod
+    def _nv12_planes(y, uv, W=None):
+        """(y, uv) uint8 [B,H,pitch] / [B,H/2,pitch] -> (keepalive, y address, uv address, B, H, W, pitch, frame_stride).  Planes that
+        are views of one surface (rows `pitch` bytes apart, both with the same frame stride) are passed as they lie; anything else is
+        copied into one [B, 3H/2, pitch] surface.  W defaults to the pitch."""
+        y, uv = np.asarray(y), np.asarray(uv)
+        assert y.dtype == np.uint8 and uv.dtype == np.uint8 and y.ndim == 3 and uv.ndim == 3, "planes must be uint8 [B,H,pitch] / [B,H/2,pitch]"
+        B, H, pitch = y.shape
+        assert uv.shape == (B, H // 2, pitch) and H % 2 == 0, "uv must be [B,H/2,pitch] with y's pitch"
+        W = pitch if W is None else int(W)
+        in_place = (y.strides[1:] == (pitch, 1) and uv.strides[1:] == (pitch, 1) and (B == 1 or (y.strides[0] == uv.strides[0] and y.strides[0] > 0)))
+        if not in_place:
+            surf = np.concatenate([y, uv], axis=1)
+            y, uv = surf[:, :H], surf[:, H:]
+        return (y, uv), y.ctypes.data, uv.ctypes.data, B, H, W, pitch, (y.strides[0] if B > 1 else 0)
+
+    def track_step_nv12(self, y, uv, hand_side, W=None, want_kpmap=False):
+        """track_step on NV12 frames: y [B,H,pitch], uv [B,H/2,pitch] uint8 (W: the picture's width where pitch > W).  Every output
+        equals track_step_u8 on nv12_to_rgb(y, uv) bit for bit; no RGB frame is built."""
+        keep, py, puv, B, H, W, pitch, fs = self._nv12_planes(y, uv, W)
+        hand_side = _f32(hand_side)
+        assert hand_side.shape == (B, 2), "hand_side must be [B,2]"
+        o = self._track_outputs(B, want_kpmap)
+        self._chk(self.lib.hp3d_track_step_nv12(self.h, B, H, W, C.c_void_p(py), C.c_void_p(puv), pitch, fs, _ptr(hand_side),
+                                                *[_ptr(o[k]) for k in self._TRACK_ORDER]))
+        return o
+
+    def track_step_nv12_dev(self, B, H, W, y_ptr, uv_ptr, pitch, frame_stride, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0, coord3d=0,
+                            kp_crop=0, kp_hw=0, confidence=0, lost=0, detected=0):
+        """Device-pointer variant (ints): the surfaces are read in place; stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_step_nv12_dev(self.h, B, H, W, v(y_ptr), v(uv_ptr), int(pitch), int(frame_stride), v(hand_side_ptr),
+                                                    v(crop), v(scale), v(center), v(kpmap), v(coord3d), v(kp_crop), v(kp_hw), v(confidence),
+                                                    v(lost), v(detected)))
+
+    def track_hands_step_nv12(self, y, uv, hand_side, max_hands, W=None, want_kpmap=False):
+        """track_hands_step on NV12 frames (as track_step_nv12); equals track_hands_step_u8 on the converted frames bit for bit."""
+        keep, py, puv, B, H, W, pitch, fs = self._nv12_planes(y, uv, W)
+        hand_side = _f32(hand_side)
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._track_hands_outputs(B, K, want_kpmap)
+        self._chk(self.lib.hp3d_track_hands_step_nv12(self.h, B, H, W, C.c_void_p(py), C.c_void_p(puv), pitch, fs, K, _ptr(hand_side),
+                                                      *[_ptr(o[k]) for k in self._TRACK_HANDS_ORDER]))
+        return o
+
+    def track_hands_step_nv12_dev(self, B, H, W, K, y_ptr, uv_ptr, pitch, frame_stride, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0,
+                                  coord3d=0, kp_crop=0, kp_hw=0, confidence=0, lost=0, detected=0, valid=0, area=0, claimed=0):
+        """Device-pointer variant (ints): the surfaces are read in place; stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_hands_step_nv12_dev(self.h, B, H, W, v(y_ptr), v(uv_ptr), int(pitch), int(frame_stride), int(K),
+                                                          v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap), v(coord3d), v(kp_crop),
+                                                          v(kp_hw), v(confidence), v(lost), v(detected), v(valid), v(area), v(claimed)))
+
+    def nv12_to_rgb(self, y, uv, W=None):
+        """NV12 planes -> uint8 RGB [B,H,W,3] by the rule of include/hp3d.h (option "nv12_matrix")."""
+        keep, py, puv, B, H, W, pitch, fs = self._nv12_planes(y, uv, W)
+        out = np.empty((B, H, W, 3), np.uint8)
+        self._chk(self.lib.hp3d_nv12_to_rgb(self.h, C.c_void_p(py), C.c_void_p(puv), B, H, W, pitch, fs, _ptr(out)))
+        return out
+
+    def crop_and_resize_nv12(self, y, uv, center, scale, W=None, K=1, idx=None, crop_size=256):
+        """crop_and_resize straight from NV12 frames: center [B*K,2], scale [B*K], K boxes per frame -> [B*K,crop,crop,3]; with idx
+        [m] (slot indices) the crops idx[i] only -> [m,crop,crop,3].  = crop_and_resize_u8 / crop_and_resize_idx on nv12_to_rgb."""
+        keep, py, puv, B, H, W, pitch, fs = self._nv12_planes(y, uv, W)
+        center, scale = _f32(center).reshape(-1, 2), _f32(scale).reshape(-1)
+        assert center.shape[0] == B * int(K) and scale.shape[0] == B * int(K), "center / scale must hold B*K boxes"
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B * int(K) if idx is None else idx.size
+        out = np.empty((n, crop_size, crop_size, 3), np.float32)
+        self._chk(self.lib.hp3d_crop_and_resize_nv12(self.h, C.c_void_p(py), C.c_void_p(puv), B, H, W, pitch, fs, int(K), _ptr(center),
+                                                     _ptr(scale), _ptr(idx), 0 if idx is None else int(idx.size), int(crop_size), _ptr(out)))
+        return out
+
+    def downscale_nv12(self, y, uv, f, W=None, idx=None):
+        """The detection frame of NV12 frames [B or m,ceil(H/f),ceil(W/f),3] (f = 1: the normalised frame); idx: the frames idx[i]
+        only.  = downscale_u8 (f = 1: preprocess_u8 at equal sizes) on nv12_to_rgb, bit for bit."""
+        keep, py, puv, B, H, W, pitch, fs = self._nv12_planes(y, uv, W)
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B if idx is None else idx.size
+        out = np.empty((n, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
+        self._chk(self.lib.hp3d_downscale_nv12(self.h, C.c_void_p(py), C.c_void_p(puv), B, H, W, pitch, fs, int(f), _ptr(idx),
+                                               0 if idx is None else int(idx.size), _ptr(out)))
+        return out
 
     def track_box(self, keypoint_hw, H, W, score32=None, margin=None):
         """The next crop box from 21 image-space keypoints [B,21,2] (row, col): (center [B,2], scale [B], confidence [B], lost [B]).

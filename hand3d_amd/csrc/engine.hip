@@ -286,6 +286,8 @@ struct Options {
                                     // hand only; 0: every slot runs, absent ones on their fall-back crop
     int track_partial_detect = 0;   // option "track_partial_detect": a detect step of hp3d_track_step* that only `lost` flags caused runs HandSegNet,
                                     // the soft-max and the mask growth on the lost frames only; 0: on the whole batch
+    int nv12_matrix = 0;            // option "nv12_matrix": the colour matrix of NV12 frames: 0 "bt709" (default), 1 "bt601",
+                                    // 2 "bt709_full", 3 "bt601_full" (nv12_matrix_index)
 };
 
 // Launch counters (hp3d_get_counter: which kernels really ran).
@@ -319,6 +321,7 @@ struct Counters {
     long hands_compact_waits = 0;                   // ... and the stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*)
     long track_partial_frames_run = 0, track_partial_frames_skipped = 0;   // option "track_partial_detect": frames of partial chunks HandSegNet ran on / did not
     long frame_gather_launches = 0;                 // ... and the launches of frame_gather_kernel (the step and hp3d_gather_frames)
+    long crop_nv12_launches = 0;                    // crops taken straight from an NV12 frame (either crop_and_resize*_nv12_kernel)
 };
 
 // Option "hands_compact" (DESIGN.md 4.15).  h_map: two page-locked buffers used in turn, idx [cap] | pos [cap] of one chunk; a buffer is
@@ -421,6 +424,7 @@ struct hp3d_ctx : Options, Counters {
     unsigned char* d_det = nullptr;
     unsigned char* d_u8 = nullptr;
     size_t u8_bytes = 0;
+    std::vector<unsigned char> h_nv12;               // host NV12 planes with a pitch above W, packed tight for their upload
     size_t image_floats = 0, large_floats = 0, det_bytes = 0, pose_px = 0;
 
     // profiling
@@ -1812,13 +1816,124 @@ int ensure_stage(hp3d_ctx* ctx, size_t floats) {
     }
     return 0;
 }
+// ---- NV12 frames (layout and colour rule: include/hp3d.h) ------------------------------------------------------------
+// What the caller handed over: frame 0's planes (host or device pointers), the row pitch, the frame stride.
+struct Nv12Arg {
+    const unsigned char* y;
+    const unsigned char* uv;
+    int pitch;
+    long long frame_stride;
+};
+// every refusal comes before anything is enqueued
+int check_nv12(hp3d_ctx* ctx, int B, int H, int W, const Nv12Arg& a) {
+    if (!a.y) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12: y (the luma plane) is NULL");
+    if (!a.uv) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12: uv (the chroma plane) is NULL");
+    if (B < 1 || H < 16 || W < 16) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad shape B=%d H=%d W=%d (need B>=1, H,W >=16)", B, H, W);
+    if ((H | W) & 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12: H=%d and W=%d must be even (a chroma sample covers 2 x 2 pixels)", H, W);
+    if (a.pitch < W) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12: pitch=%d is below W=%d", a.pitch, W);
+    if (B > 1 && a.frame_stride < (long long)a.pitch * (H - 1) + W)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12: frame_stride=%lld is below pitch * (H - 1) + W = %lld", a.frame_stride, (long long)a.pitch * (H - 1) + W);
+    return 0;
+}
+// Host planes -> d_u8, packed tight on the way (frame b: H rows of W luma bytes, then H / 2 rows of W chroma bytes; 1.5 bytes a pixel).
+// Only bytes [0, W) of a row are read: planes at pitch W are uploaded as they lie, wider ones are packed row by row on the host first.
+int upload_nv12(hp3d_ctx* ctx, int B, int H, int W, const Nv12Arg& a, Nv12Src* out) {
+    const size_t ny = (size_t)H * W, nc = (size_t)(H / 2) * W, fs = ny + nc, nbytes = fs * B;
+    if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
+    const size_t stride = B > 1 ? (size_t)a.frame_stride : 0;
+    if (a.pitch == W) {
+        for (int b = 0; b < B; ++b) {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8 + b * fs, a.y + b * stride, ny, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8 + b * fs + ny, a.uv + b * stride, nc, hipMemcpyHostToDevice, ctx->stream));
+        }
+    } else {
+        // (the previous call's upload has completed: every host form ends on a stream synchronise)
+        ctx->h_nv12.resize(nbytes);
+        for (int b = 0; b < B; ++b) {
+            unsigned char* d = ctx->h_nv12.data() + b * fs;
+            for (int r = 0; r < H; ++r) memcpy(d + (size_t)r * W, a.y + b * stride + (size_t)r * a.pitch, W);
+            for (int r = 0; r < H / 2; ++r) memcpy(d + ny + (size_t)r * W, a.uv + b * stride + (size_t)r * a.pitch, W);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, ctx->h_nv12.data(), nbytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *out = nv12_src(ctx->d_u8, ctx->d_u8 + ny, W, fs, ctx->nv12_matrix);
+    return 0;
+}
+
+// The frames of a chunk of a tracking step: float32, uint8 or NV12 -- exactly one is set.  The wrappers below switch on the kind, so
+// the three-way branch is written once; the float32 and uint8 launches, profile rows and counters are the ones they were.
+struct FrameSrc {
+    const float* f32 = nullptr;
+    const unsigned char* u8 = nullptr;
+    const Nv12Src* nv12 = nullptr;
+};
+// the nb * K crops of nb frames, K boxes per frame, into d_crop
+int crop_frames(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* bc, const float* bs) {
+    const int ns = nb * K;
+    if (src.nv12) {
+        ProfScope ps(ctx, "crop_and_resize_nv12", "crop_and_resize_nv12", 0.0, 1.5 * nb * H * W + 4.0 * ns * 256 * 256 * 3);
+        crop_and_resize_nv12_launch(*src.nv12, ns, H, W, bc, bs, nullptr, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_nv12_launches;
+    } else if (src.u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
+        ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
+        crop_and_resize_u8_launch(src.u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+        ++ctx->crop_u8_launches;
+    } else {
+        ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
+        crop_and_resize_launch(src.f32, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+// the m crops of the slots idx[i] (option "hands_compact"), dense, into d_crop
+int crop_frames_idx(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* center, const float* scale, const int* d_idx,
+                    int m) {
+    if (src.nv12) {
+        ProfScope ps(ctx, "crop_and_resize_idx_nv12", "crop_and_resize_idx_nv12", 0.0, 1.5 * nb * H * W + 4.0 * m * 256 * 256 * 3);
+        crop_and_resize_nv12_launch(*src.nv12, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_nv12_launches;
+    } else if (src.u8) {
+        ProfScope ps(ctx, "crop_and_resize_idx_u8", "crop_and_resize_idx_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * m * 256 * 256 * 3);
+        crop_and_resize_idx_u8_launch(src.u8, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_u8_launches;
+    } else {
+        ProfScope ps(ctx, "crop_and_resize_idx", "crop_and_resize_idx", 0.0, 4.0 * ((double)nb * H * W * 3 + (double)m * 256 * 256 * 3));
+        crop_and_resize_idx_launch(src.f32, m, H, W, 3, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+// a raw frame as the normalised float32 frame in d_image: all nb frames (idx null) or the frames idx[i], i < nb, dense
+int normalise_frames(hp3d_ctx* ctx, const FrameSrc& src, const int* idx, int nb, int H, int W) {
+    if (src.nv12) {
+        const char* row = idx ? "preprocess_nv12_idx" : "preprocess_nv12";
+        ProfScope ps(ctx, row, row, 0.0, 1.5 * nb * H * W + 4.0 * nb * H * W * 3);
+        downscale_nv12_launch(*src.nv12, idx, nb, H, W, 1, ctx->d_image, ctx->stream);
+    } else if (idx) {
+        ProfScope ps(ctx, "preprocess_u8_idx", "preprocess_u8_idx", 0.0, 5.0 * nb * H * W * 3);
+        preprocess_u8_idx_launch(src.u8, idx, nb, H, W, ctx->d_image, ctx->stream);
+    } else {
+        ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
+        preprocess_u8_launch(src.u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 // the front of such a detect step: the detection frame into d_image, detection at (nb, Hd, Wd), the boxes of `slots` slots to the frame
-// idx (option "track_partial_detect", K = 0): nb = the number of frames that detect, frame i of them is d_img / d_u8's frame idx[i]; the
+// idx (option "track_partial_detect", K = 0): nb = the number of frames that detect, frame i of them is the source's frame idx[i]; the
 // boxes come out dense
-int run_detect_reduced(hp3d_ctx* ctx, const float* d_img, const unsigned char* d_u8, int nb, int H, int W, int Hd, int Wd, int K = 0,
+int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W, int Hd, int Wd, int K = 0,
                        const MaskKeep& mk = MaskKeep(), const int* idx = nullptr) {
     const int f = ctx->detect_scale, slots = nb * std::max(K, 1);
-    if (idx) {
+    const float* d_img = src.f32;
+    const unsigned char* d_u8 = src.u8;
+    if (src.nv12) {
+        const char* row = idx ? "downscale_nv12_idx" : "downscale_nv12";
+        ProfScope ps(ctx, row, row, 0.0, 1.5 * nb * H * W + 4.0 * nb * Hd * Wd * 3);
+        downscale_nv12_launch(*src.nv12, idx, nb, H, W, f, ctx->d_image, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+    } else if (idx) {
         const char* row = d_u8 ? "downscale_u8_idx" : "downscale_idx";
         ProfScope ps(ctx, row, row, 0.0, (double)nb * H * W * 3 * (d_u8 ? 1.0 : 4.0) + 4.0 * nb * Hd * Wd * 3);
         if (d_u8) downscale_u8_idx_launch(d_u8, idx, nb, H, W, f, ctx->d_image, ctx->stream);
@@ -1858,9 +1973,11 @@ int run_detect_reduced(hp3d_ctx* ctx, const float* d_img, const unsigned char* d
 //  the copy_out sequence here belongs there as well.)
 int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, const unsigned char* image_u8, const float* hand_side,
                     float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
-                    double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev) {
-    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+                    double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev, const Nv12Arg* nv = nullptr) {
+    if ((!image && !image_u8 && !nv) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (nv) CHK(check_nv12(ctx, B, H, W, *nv));
     CHK(check_img(ctx, B, H, W));
+    const bool raw = image_u8 || nv;                     // uint8 or NV12 frames: no float32 frame comes in
     int Hd, Wd;
     CHK(detect_frame(ctx, H, W, &Hd, &Wd));
     const int f = ctx->detect_scale;
@@ -1881,7 +1998,7 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     // option "track_partial_detect": only a detect step that `lost` flags alone caused (a fresh or scheduled one re-boxes every image)
     const bool partial_step = ctx->track_partial_detect && detect && !force_all;
     // a host float32 frame is staged where the detection frame (f > 1) or the gathered lost frames (a partial chunk) go to d_image
-    if ((f > 1 || partial_step) && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    if ((f > 1 || partial_step) && !dev && !raw) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track(ctx, B));
     T.valid = false;                                     // a step that fails half way leaves no boxes behind
     if (image_u8) {
@@ -1889,6 +2006,9 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
         if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
     }
+    Nv12Src nvs{};                                       // NV12 frames: the caller's surfaces in place (dev) or their packed upload
+    if (nv && dev) nvs = nv12_src(nv->y, nv->uv, nv->pitch, B > 1 ? (size_t)nv->frame_stride : 0, ctx->nv12_matrix);
+    else if (nv) CHK(upload_nv12(ctx, B, H, W, *nv, &nvs));
     const int saved_prof = ctx->profiling;
     struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
     if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
@@ -1909,12 +2029,15 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
         if (!dev) {
             CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * 2, false));
             d_hs = ctx->d_hs;
-            if (!image_u8) {
+            if (!raw) {
                 float* stage = (f > 1 || partial) ? ctx->d_stage : ctx->d_image;
                 CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
                 d_img = stage;
             }
         }
+        const Nv12Src nvc = nvs.at(b0);
+        FrameSrc src;
+        src.f32 = d_img; src.u8 = d_u8; src.nv12 = nv ? &nvc : nullptr;
         float* bc = T.center[cur] + (size_t)b0 * 2;
         float* bs = T.scale[cur] + b0;
         int* pidx = T.pidx + b0;
@@ -1928,11 +2051,10 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
             ctx->track_partial_frames_skipped += nb - m;
             // the m lost frames, dense, into d_image: never the buffer the chunk's frames lie in (a host frame was staged in d_stage)
             if (f > 1) {
-                CHK(run_detect_reduced(ctx, d_img, d_u8, m, H, W, Hd, Wd, 0, MaskKeep(), pidx));
+                CHK(run_detect_reduced(ctx, src, m, H, W, Hd, Wd, 0, MaskKeep(), pidx));
             } else {
-                if (image_u8) {
-                    ProfScope ps(ctx, "preprocess_u8_idx", "preprocess_u8_idx", 0.0, 5.0 * m * H * W * 3);
-                    preprocess_u8_idx_launch(d_u8, pidx, m, H, W, ctx->d_image, ctx->stream);
+                if (raw) {
+                    CHK(normalise_frames(ctx, src, pidx, m, H, W));
                 } else {
                     ProfScope ps(ctx, "frame_gather", "frame_gather", 0.0, 8.0 * m * H * W * 3);
                     frame_gather_launch(d_img, pidx, m, (size_t)H * W * 3, ctx->d_image, ctx->stream);
@@ -1945,49 +2067,28 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
                 ProfScope ps(ctx, "track_select_pos", "track_select_pos", 0.0, 16.0 * nb);
                 track_select_pos_launch(T.lost + b0, ppos, ctx->d_center, ctx->d_scale, nb, bc, bs, T.detected + b0, ctx->stream);
             }
-            if (image_u8) {          // all nb crops straight from the uint8 frame (= normalise, then crop: bit for bit)
-                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
-                crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
-                ++ctx->crop_u8_launches;
-            } else {
-                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
-                crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
-            }
+            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));          // (a raw frame: all nb crops straight from it = normalise, then crop, bit for bit)
         } else if (chunk_detect && f > 1) {
-            CHK(run_detect_reduced(ctx, d_img, d_u8, nb, H, W, Hd, Wd));
+            CHK(run_detect_reduced(ctx, src, nb, H, W, Hd, Wd));
             {
                 ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
                 track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
             }
-            if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
-                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
-                crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
-                ++ctx->crop_u8_launches;
-            } else {
-                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
-                crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
-            }
+            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));
         } else if (chunk_detect) {
-            if (image_u8) {
-                ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
-                preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
-                HIPCHK(ctx, hipGetLastError());
+            if (raw) {
+                CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
                 d_img = ctx->d_image;
             }
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, image_u8 != nullptr, false));
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, raw, false));
             {
                 ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
                 track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
             }
             ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
             crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
-        } else if (image_u8) {
-            ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * 256 * 256 * 3);
-            crop_and_resize_u8_launch(d_u8, nb, H, W, bc, bs, 256, ctx->d_crop, ctx->stream);
-            ++ctx->crop_u8_launches;
         } else {
-            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
-            crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
+            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));
         }
         HIPCHK(ctx, hipGetLastError());
         CHK(run_posenet(ctx, ctx->d_crop, nb, 256, 256, true));
@@ -2107,6 +2208,8 @@ struct CompactChunk {
     bool want_kp;                        // run kp_detect (hp3d_infer_hands*: only when asked for; the tracker: always)
     // the multi-hand tracker's box step (null: hp3d_infer_hands*): the chunk's slice of the state
     const std::function<void(const double* kp_image_dense, const int* pos)>* box = nullptr;
+    const Nv12Src* nv12 = nullptr;       // ... or NV12: d_img and d_u8 are then unused
+    FrameSrc src() const { FrameSrc f; f.f32 = d_img; f.u8 = d_u8; f.nv12 = nv12; return f; }
 };
 
 // The back half at batch m = the chunk's valid slots.  *compacted = false (m = ns: no absent slot): nothing is enqueued, the caller
@@ -2147,15 +2250,7 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
             ProfScope ps(ctx, "slot_gather", "slot_gather", 0.0, 24.0 * m);
             slot_gather_launch(d_idx, m, c.hand_side, c.center, c.scale, Q.d_hs, Q.d_center, Q.d_scale, ctx->stream);
         }
-        if (c.d_u8) {
-            ProfScope ps(ctx, "crop_and_resize_idx_u8", "crop_and_resize_idx_u8", 0.0, 1.0 * c.nb * c.H * c.W * 3 + 4.0 * m * 256 * 256 * 3);
-            crop_and_resize_idx_u8_launch(c.d_u8, m, c.H, c.W, c.center, c.scale, d_idx, c.K, 256, ctx->d_crop, ctx->stream);
-            ++ctx->crop_u8_launches;
-        } else {
-            ProfScope ps(ctx, "crop_and_resize_idx", "crop_and_resize_idx", 0.0, 4.0 * ((double)c.nb * c.H * c.W * 3 + (double)m * 256 * 256 * 3));
-            crop_and_resize_idx_launch(c.d_img, m, c.H, c.W, 3, c.center, c.scale, d_idx, c.K, 256, ctx->d_crop, ctx->stream);
-        }
-        HIPCHK(ctx, hipGetLastError());
+        CHK(crop_frames_idx(ctx, c.src(), c.nb, c.K, c.H, c.W, c.center, c.scale, d_idx, m));
         CHK(run_posenet(ctx, ctx->d_crop, m, 256, 256, true));
         const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
             if (c.kp_scoremap) {
@@ -2205,17 +2300,7 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
 // The crop of every slot of a chunk, for a compacted call's chunk without an absent slot: the launch and the profile row of the
 // uncompacted path.
 int crop_all_slots(hp3d_ctx* ctx, const CompactChunk& c) {
-    const int ns = c.nb * c.K;
-    if (c.d_u8) {
-        ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * c.nb * c.H * c.W * 3 + 4.0 * ns * 256 * 256 * 3);
-        crop_and_resize_u8_launch(c.d_u8, ns, c.H, c.W, c.center, c.scale, 256, ctx->d_crop, ctx->stream, c.K);
-        ++ctx->crop_u8_launches;
-    } else {
-        ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * c.nb * (c.H * c.W * 3 + c.K * 256 * 256 * 3));
-        crop_and_resize_launch(c.d_img, ns, c.H, c.W, 3, c.center, c.scale, 256, ctx->d_crop, ctx->stream, c.K);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return 0;
+    return crop_frames(ctx, c.src(), c.nb, c.K, c.H, c.W, c.center, c.scale);
 }
 
 // Up to K hands per frame: HandSegNet, the soft-max and ONE multi-hand mask growth per chunk of frames, then the back
@@ -2363,10 +2448,12 @@ void track_hands_free(hp3d_ctx* ctx) {
 int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, const float* hand_side,
                           float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
                           double* kp_image, float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area,
-                          int32_t* claimed, bool dev) {
-    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+                          int32_t* claimed, bool dev, const Nv12Arg* nv = nullptr) {
+    if ((!image && !image_u8 && !nv) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    if (nv) CHK(check_nv12(ctx, B, H, W, *nv));
     CHK(check_img(ctx, B, H, W));
+    const bool raw = image_u8 || nv;                     // uint8 or NV12 frames: no float32 frame comes in
     int Hd, Wd;
     CHK(detect_frame(ctx, H, W, &Hd, &Wd));
     const int f = ctx->detect_scale;
@@ -2393,7 +2480,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     int mb = front <= 0 ? B : std::min(front, B);
     if (back > 0) mb = std::min(mb, std::max(1, back / K));
     CHK(ensure_arena(ctx, mb, Hd, Wd, mb * K));
-    if (f > 1 && !dev && !image_u8) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    if (f > 1 && !dev && !raw) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track_hands(ctx, n));
     T.ok = false;                                        // a step that fails half way leaves no state behind
     T.B = B; T.K = K; T.H = H; T.W = W; T.f = f;         // (the flags' layout: lost() = flags + B K)
@@ -2403,6 +2490,9 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
         if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
     }
+    Nv12Src nvs{};                                       // NV12 frames: the caller's surfaces in place (dev) or their packed upload
+    if (nv && dev) nvs = nv12_src(nv->y, nv->uv, nv->pitch, B > 1 ? (size_t)nv->frame_stride : 0, ctx->nv12_matrix);
+    else if (nv) CHK(upload_nv12(ctx, B, H, W, *nv, &nvs));
     const int saved_prof = ctx->profiling;
     struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
     if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
@@ -2418,42 +2508,35 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
         if (!dev) {
             CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false));
             d_hs = ctx->d_hs;
-            if (!image_u8) {
+            if (!raw) {
                 float* stage = f > 1 ? ctx->d_stage : ctx->d_image;
                 CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
                 d_img = stage;
             }
         }
+        const Nv12Src nvc = nvs.at(b0);
+        FrameSrc src;
+        src.f32 = d_img; src.u8 = d_u8; src.nv12 = nv ? &nvc : nullptr;
         float* bc = T.center[cur] + s0 * 2;
         float* bs = T.scale[cur] + s0;
         if (detect && f > 1) {
             MaskKeep mk;
             mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
-            CHK(run_detect_reduced(ctx, d_img, d_u8, nb, H, W, Hd, Wd, K, mk));
+            CHK(run_detect_reduced(ctx, src, nb, H, W, Hd, Wd, K, mk));
             {
                 ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
                 track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
                                           T.detected + s0, T.area + s0, ctx->stream);
             }
-            if (comp) {              // (the crop follows the flags, below)
-            } else if (image_u8) {          // the crop comes from the frame itself: no normalised full-size frame exists
-                ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
-                crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
-                ++ctx->crop_u8_launches;
-            } else {
-                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
-                crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
-            }
+            if (!comp) CHK(crop_frames(ctx, src, nb, K, H, W, bc, bs));          // (comp: the crop follows the flags, below)
         } else if (detect) {
-            if (image_u8) {
-                ProfScope ps(ctx, "preprocess_u8", "preprocess_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * nb * H * W * 3);
-                preprocess_u8_launch(d_u8, nb, H, W, H, W, ctx->d_image, ctx->stream);
-                HIPCHK(ctx, hipGetLastError());
+            if (raw) {
+                CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
                 d_img = ctx->d_image;
             }
             MaskKeep mk;
             mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, image_u8 != nullptr, false, K, mk));
+            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, raw, false, K, mk));
             {
                 ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
                 track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
@@ -2463,14 +2546,8 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
                 ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
                 crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
             }
-        } else if (comp) {           // (a tracked step: the state's flags are on the host already)
-        } else if (image_u8) {
-            ProfScope ps(ctx, "crop_and_resize_u8", "crop_and_resize_u8", 0.0, 1.0 * nb * H * W * 3 + 4.0 * ns * 256 * 256 * 3);
-            crop_and_resize_u8_launch(d_u8, ns, H, W, bc, bs, 256, ctx->d_crop, ctx->stream, K);
-            ++ctx->crop_u8_launches;
-        } else {
-            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
-            crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
+        } else if (!comp) {          // (comp, a tracked step: the state's flags are on the host already)
+            CHK(crop_frames(ctx, src, nb, K, H, W, bc, bs));
         }
         HIPCHK(ctx, hipGetLastError());
         float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
@@ -2489,6 +2566,8 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
             };
             CompactChunk cc{nb, K, H, W, T.h_flags + s0, d_img, image_u8 && (!detect || f > 1) ? d_u8 : nullptr, bc, bs, d_hs,
                             off(image_crop, 256 * 256 * 3), kpmap_out, off(coord3d, 63), kpc_out, kpi_out, dev, true, &box};
+            // (likewise an NV12 frame; where the crop comes from the frame, d_img is not read)
+            cc.nv12 = (nv && (!detect || f > 1)) ? &nvc : nullptr;
             if (detect) CHK(compact_wait_flags(ctx, T.valid() + s0, ns, &cc.h_valid));
             CHK(run_compact_back_half(ctx, cc, &compacted));
             if (!compacted) CHK(crop_all_slots(ctx, cc));
@@ -2858,6 +2937,12 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
     if (k == "track_partial_detect") {
         if (v != "0" && v != "1") HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_partial_detect wants 0 or 1, got %s", value);
         ctx->track_partial_detect = v == "1";
+        return 0;
+    }
+    if (k == "nv12_matrix") {
+        const int m = nv12_matrix_index(value);
+        if (m < 0) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12_matrix wants bt709, bt601, bt709_full or bt601_full, got %s", value);
+        ctx->nv12_matrix = m;
         return 0;
     }
     if (k == "track_redetect") {
@@ -3300,6 +3385,25 @@ int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8
                                  keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false);
 }
 
+int hp3d_track_hands_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride, int K,
+                               const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                               float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                               int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    return track_hands_step_impl(ctx, B, H, W, K, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false, &nv);
+}
+int hp3d_track_hands_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                                   int K, const float* hand_side, float* image_crop, float* scale_crop, float* center,
+                                   float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw,
+                                   float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    return track_hands_step_impl(ctx, B, H, W, K, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
+                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, true, &nv);
+}
+
 int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
                          const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
                          float* confidence, int32_t* lost) {
@@ -3384,6 +3488,25 @@ int hp3d_track_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* im
         HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "tracking crops straight from the uint8 frame: the frame (%dx%d) must have the network size (%dx%d)", Hin, Win, H, W);
     return track_step_impl(ctx, B, H, W, nullptr, image_u8, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
                            keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false);
+}
+
+int hp3d_track_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                         const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                         float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                         int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    return track_step_impl(ctx, B, H, W, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d,
+                           keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false, &nv);
+}
+int hp3d_track_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                             const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                             float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                             int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    return track_step_impl(ctx, B, H, W, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d,
+                           keypoint_hw_crop, keypoint_hw, confidence, lost, detected, true, &nv);
 }
 
 int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw, const float* score32, float margin, float* center,
@@ -3531,6 +3654,87 @@ int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u
         if (f > 1) downscale_idx_launch(d_x, d_i, m, H, W, f, d_o, ctx->stream);
         else { frame_gather_launch(d_x, d_i, m, (size_t)H * W * 3, d_o, ctx->stream); ++ctx->frame_gather_launches; }
     }
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+// ---- NV12 frames: the per-op forms ---------------------------------------------------------------------------
+// Host planes at the caller's pitch and stride -> the same layout on the device (the kernels run on the pitch they were given); only
+// bytes [0, W) of a row are read on the host too: the rows are placed into a zeroed span that is then uploaded.
+static int upload_nv12_as_is(hp3d_ctx* ctx, Scratch& S, int B, int H, int W, const Nv12Arg& a, Nv12Src* out) {
+    const size_t stride = B > 1 ? (size_t)a.frame_stride : 0;
+    const size_t span_y = stride * (B - 1) + (size_t)a.pitch * (H - 1) + W, span_c = stride * (B - 1) + (size_t)a.pitch * (H / 2 - 1) + W;
+    std::vector<unsigned char>& h = ctx->h_nv12;
+    h.assign(span_y + span_c, 0);
+    for (int b = 0; b < B; ++b) {
+        for (int r = 0; r < H; ++r) memcpy(&h[b * stride + (size_t)r * a.pitch], a.y + b * stride + (size_t)r * a.pitch, W);
+        for (int r = 0; r < H / 2; ++r) memcpy(&h[span_y + b * stride + (size_t)r * a.pitch], a.uv + b * stride + (size_t)r * a.pitch, W);
+    }
+    unsigned char* d = S.upload(h.data(), h.size()); NN(ctx, d);
+    *out = nv12_src(d, d + span_y, a.pitch, stride, ctx->nv12_matrix);
+    return 0;
+}
+int hp3d_nv12_to_rgb(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, uint8_t* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    CHK(check_nv12(ctx, B, H, W, nv));
+    if (!out) HP3D_FAIL(ctx, HP3D_ERR_ARG, "nv12_to_rgb: out is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    Nv12Src src;
+    CHK(upload_nv12_as_is(ctx, S, B, H, W, nv, &src));
+    const size_t no = (size_t)B * H * W * 3;
+    unsigned char* d_o = S.alloc<unsigned char>(no); NN(ctx, d_o);
+    nv12_to_rgb_launch(src, B, H, W, d_o, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_crop_and_resize_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, int K,
+                              const float* center, const float* scale, const int32_t* idx, int m, int crop_size, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    CHK(check_nv12(ctx, B, H, W, nv));
+    if (!center || !scale || !out || K < 1 || K > HP3D_MAX_HANDS || crop_size < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_nv12: bad arguments");
+    if (idx && (m < 0 || m > B * K)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_nv12: m = %d must be in 0 ... B K = %d", m, B * K);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B * K) HP3D_FAIL(ctx, HP3D_ERR_ARG, "idx[%d] = %d is no slot of %d", i, (int)idx[i], B * K);
+    const int n = idx ? m : B * K;
+    if (n == 0) return 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    Nv12Src src;
+    CHK(upload_nv12_as_is(ctx, S, B, H, W, nv, &src));
+    const size_t no = (size_t)n * crop_size * crop_size * 3;
+    float* d_c = S.upload(center, (size_t)B * K * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)B * K); NN(ctx, d_s);
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    crop_and_resize_nv12_launch(src, n, H, W, d_c, d_s, d_i, K, crop_size, d_o, ctx->stream);
+    ++ctx->crop_nv12_launches;
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_downscale_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, int f,
+                        const int32_t* idx, int m, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
+    CHK(check_nv12(ctx, B, H, W, nv));
+    if (!out || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_nv12: bad arguments (f = %d must be in 1 ... 8)", f);
+    if (idx && (m < 1 || m > B)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_nv12: m = %d must be in 1 ... B = %d", m, B);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_nv12: idx[%d] = %d is no frame of %d", i, (int)idx[i], B);
+    const int n = idx ? m : B;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    Nv12Src src;
+    CHK(upload_nv12_as_is(ctx, S, B, H, W, nv, &src));
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const size_t no = (size_t)n * Hd * Wd * 3;
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    downscale_nv12_launch(src, d_i, n, H, W, f, d_o, ctx->stream);
     HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
@@ -4040,6 +4244,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"track_partial_frames_run", &Counters::track_partial_frames_run, false},
         {"track_partial_frames_skipped", &Counters::track_partial_frames_skipped, false},
         {"frame_gather_launches", &Counters::frame_gather_launches, false},
+        {"crop_nv12_launches", &Counters::crop_nv12_launches, false},
     };
     const std::string k(name);
     for (const auto& c : table)

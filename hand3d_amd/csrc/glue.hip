@@ -3,6 +3,7 @@
 // expressions op by op in float32 (TF 1.3 CPU/GPU kernels), and the box / interpolation
 // arithmetic feeds discontinuous decisions (row validity, floor/ceil), so no FMA contraction.
 #include "hp3d_common.h"
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -254,6 +255,31 @@ void preprocess_u8_kernel(const unsigned char* img, int B, int H, int W, int oh,
     }
 }
 
+// ---- NV12 frames ------------------------------------------------------------------------------------------------------
+// Pixel (r, c) of frame `fr` of an NV12 surface as three uint8 channels -- the one place the colour rule of include/hp3d.h is written:
+// Y = y[r pitch + c]; U, V = the byte pair at uv[(r >> 1) pitch + (c & ~1)] (one 2-byte load: chroma is replicated over its 2 x 2 block,
+// never interpolated); C = Y - yoff, D = U - 128, E = V - 128; channel = clamp((ky C + cu D + cv E + 128) >> 8, 0, 255), int32, the
+// shift arithmetic.  Only bytes [0, W) of a row are read (W even: c | 1 < W).
+struct Rgb8 { int r, g, b; };
+__device__ __forceinline__ int nv12_clamp8(int v) { return min(max(v >> 8, 0), 255); }
+__device__ __forceinline__ Rgb8 nv12_convert(const Nv12Src& P, int Y, int U, int V) {
+    const int C = P.ky * (Y - P.yoff) + 128, D = U - 128, E = V - 128;
+    Rgb8 o;
+    o.r = nv12_clamp8(C + P.rv * E);
+    o.g = nv12_clamp8(C + P.gu * D + P.gv * E);
+    o.b = nv12_clamp8(C + P.bu * D);
+    return o;
+}
+__device__ __forceinline__ Rgb8 nv12_pixel(const Nv12Src& P, size_t fr, int r, int c) {
+    const size_t fb = fr * P.frame_stride;
+    const int Y = P.y[fb + (size_t)r * P.pitch + c];
+    unsigned char uv[2];
+    __builtin_memcpy(uv, P.uv + fb + (size_t)(r >> 1) * P.pitch + (c & ~1), 2);
+    return nv12_convert(P, Y, uv[0], uv[1]);
+}
+// a uint8 channel as a network value, as preprocess_u8_kernel makes it
+__device__ __forceinline__ float u8_norm(int ch) { return (float)ch / 255.0f - 0.5f; }
+
 // crop_image_from_xy -> tf.image.crop_and_resize (utils/general.py:163-196, App. B.4).  One body for both pixel types: `tap(pixel, c)` is
 // the value of channel c of pixel `pixel` of the whole batch -- a float32 image as it is, a uint8 frame normalised as
 // preprocess_u8_kernel does at equal sizes (x / 255 - 0.5, float32 op by op), so that the crop straight from a uint8 frame equals
@@ -261,12 +287,37 @@ void preprocess_u8_kernel(const unsigned char* img, int B, int H, int W, int oh,
 // extrapolation value 0 is a normalised value.
 struct TapF32 {
     const float* img; int C;
+    static constexpr bool PIXEL = false;
     __device__ __forceinline__ float operator()(size_t pixel, int c) const { return img[pixel * C + c]; }
 };
 struct TapU8 {
     const unsigned char* img; int C;
+    static constexpr bool PIXEL = false;
     __device__ __forceinline__ float operator()(size_t pixel, int c) const { return (float)img[pixel * C + c] / 255.0f - 0.5f; }
 };
+// An NV12 tap hands back a whole pixel: its three channels come from one conversion (four conversions per output pixel, not twelve),
+// each normalised as TapU8 does -- the crop equals crop_and_resize_u8 on the converted frame bit for bit.
+struct TapNv12 {
+    Nv12Src P;
+    static constexpr bool PIXEL = true;
+    __device__ __forceinline__ void pixel(size_t fr, int r, int c, float* v) const {
+        const Rgb8 p = nv12_pixel(P, fr, r, c);
+        v[0] = u8_norm(p.r); v[1] = u8_norm(p.g); v[2] = u8_norm(p.b);
+    }
+};
+// the four taps of an output pixel of a PIXEL tap, interpolated as crop_and_resize_body does per channel
+template <class Tap>
+__device__ __forceinline__ void crop_pixel_taps(const Tap& tap, size_t fr, int ty0, int ty1, int tx0, int tx1, float ly, float lx, float* o) {
+    float tl[3], tr[3], bl[3], br[3];
+    tap.pixel(fr, ty0, tx0, tl); tap.pixel(fr, ty0, tx1, tr);
+    tap.pixel(fr, ty1, tx0, bl); tap.pixel(fr, ty1, tx1, br);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = tl[c] + (tr[c] - tl[c]) * lx;
+        const float bot = bl[c] + (br[c] - bl[c]) * lx;
+        o[c] = top + (bot - top) * ly;
+    }
+}
 template <class Tap>
 __device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H, int W, int C, const float* center, const float* scale,
                                                      int crop, float* out, int boxes_per_image) {
@@ -296,13 +347,17 @@ __device__ __forceinline__ void crop_and_resize_body(const Tap tap, int B, int H
         const int tx0 = (int)floorf(in_x), tx1 = (int)ceilf(in_x);
         const float ly = in_y - (float)ty0, lx = in_x - (float)tx0;
         // box b crops image b / boxes_per_image (the K hands of a frame come from the one frame)
-        const size_t ib = (size_t)(boxes_per_image == 1 ? b : b / boxes_per_image) * H * W;
-        for (int c = 0; c < C; ++c) {
-            const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
-            const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
-            const float top = tl + (tr - tl) * lx;
-            const float bot = bl + (br - bl) * lx;
-            o[c] = top + (bot - top) * ly;
+        if constexpr (Tap::PIXEL) {
+            crop_pixel_taps(tap, (size_t)(boxes_per_image == 1 ? b : b / boxes_per_image), ty0, ty1, tx0, tx1, ly, lx, o);
+        } else {
+            const size_t ib = (size_t)(boxes_per_image == 1 ? b : b / boxes_per_image) * H * W;
+            for (int c = 0; c < C; ++c) {
+                const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
+                const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
+                const float top = tl + (tr - tl) * lx;
+                const float bot = bl + (br - bl) * lx;
+                o[c] = top + (bot - top) * ly;
+            }
         }
     }
 }
@@ -315,6 +370,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_u8_kernel(const unsigned char* img, int B, int H, int W, const float* center, const float* scale,
                                int crop, float* out, int boxes_per_image) {
     crop_and_resize_body(TapU8{img, 3}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_nv12_kernel(const Nv12Src src, int B, int H, int W, const float* center, const float* scale, int crop, float* out,
+                                 int boxes_per_image) {
+    crop_and_resize_body(TapNv12{src}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
 }
 
 HP3D_KERNEL(256)
@@ -1671,6 +1731,106 @@ void downscale_u8_idx_kernel(const unsigned char* img, const int* idx, int m, in
     downscale_body<unsigned char, F, true>(img, m, H, W, f, Hd, Wd, wide, out, idx);
 }
 
+// The detection frame of NV12 frames: every luma pixel of the window is converted (the clamp and the floor make the rule
+// non-linear: the mean of the converted pixels is not the conversion of the mean), the three integer sums are exact, the finish is the
+// uint8 frames' -- downscale_u8 on the converted frame bit for bit.  F > 0 (f = 2, 4, 8 with `wide`: both plane bases, the pitch and the
+// frame stride multiples of F): a full window row is ONE F-byte load of Y, and the window's chroma row -- F / 2 pairs, shared by two luma
+// rows (y0 is even) -- ONE F-byte load per two luma rows.  Odd f, ragged windows and unaligned surfaces: pixel by pixel.
+template <int F, bool IDX>
+__device__ __forceinline__ void downscale_nv12_body(const Nv12Src P, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
+                                                    const int* idx) {
+    constexpr int NB = F > 0 ? F : 1;
+    const long total = (long)B * Hd * Wd;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wd);
+        long r = i / Wd;
+        const int y = (int)(r % Hd);
+        const int b = (int)(r / Hd);
+        const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
+        const size_t sb = (size_t)(IDX ? idx[b] : b);
+        unsigned s0 = 0, s1 = 0, s2 = 0;
+        bool done = false;
+        if constexpr (F > 0) if (wide && nx == F) {
+            done = true;
+            const size_t fb = sb * P.frame_stride;
+            for (int yy = y0; yy < y1; yy += 2) {          // (H and y0 are even: rows come in pairs that share a chroma row)
+                unsigned char uv[NB], ya[NB], yb[NB];
+                __builtin_memcpy(uv, __builtin_assume_aligned(P.uv + fb + (size_t)(yy >> 1) * P.pitch + x0, NB), NB);
+                __builtin_memcpy(ya, __builtin_assume_aligned(P.y + fb + (size_t)yy * P.pitch + x0, NB), NB);
+                __builtin_memcpy(yb, __builtin_assume_aligned(P.y + fb + (size_t)(yy + 1) * P.pitch + x0, NB), NB);
+#pragma unroll
+                for (int k = 0; k < NB; ++k) {
+                    const Rgb8 pa = nv12_convert(P, ya[k], uv[k & ~1], uv[k | 1]);
+                    const Rgb8 pb = nv12_convert(P, yb[k], uv[k & ~1], uv[k | 1]);
+                    s0 += pa.r + pb.r; s1 += pa.g + pb.g; s2 += pa.b + pb.b;
+                }
+            }
+        }
+        if (!done) {
+            for (int yy = y0; yy < y1; ++yy)
+                for (int k = 0; k < nx; ++k) {
+                    const Rgb8 p = nv12_pixel(P, sb, yy, x0 + k);
+                    s0 += p.r; s1 += p.g; s2 += p.b;
+                }
+        }
+        const float n = (float)((y1 - y0) * nx);
+        float* o = out + (size_t)i * 3;
+        o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
+    }
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_nv12_kernel(const Nv12Src src, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_nv12_body<F, false>(src, B, H, W, f, Hd, Wd, wide, out, nullptr);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_nv12_idx_kernel(const Nv12Src src, const int* idx, int m, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_nv12_body<F, true>(src, m, H, W, f, Hd, Wd, wide, out, idx);
+}
+
+// NV12 -> the normalised float32 frame (preprocess_u8 at equal sizes on the converted frame, bit for bit) and NV12 -> uint8 RGB.  One
+// thread takes the two pixels of a chroma pair: one 2-byte load of Y, one of UV; output frame b comes from source frame idx[b] (IDX).
+template <bool IDX>
+HP3D_KERNEL(256)
+void preprocess_nv12_kernel(const Nv12Src P, const int* idx, int B, int H, int W, float* out) {
+    const int W2 = W / 2;
+    const long total = (long)B * H * W2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W2) * 2;
+        long r = i / W2;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const size_t fb = (size_t)(IDX ? idx[b] : b) * P.frame_stride;
+        unsigned char yy[2], uv[2];
+        __builtin_memcpy(yy, P.y + fb + (size_t)y * P.pitch + x, 2);
+        __builtin_memcpy(uv, P.uv + fb + (size_t)(y >> 1) * P.pitch + x, 2);
+        const Rgb8 p0 = nv12_convert(P, yy[0], uv[0], uv[1]), p1 = nv12_convert(P, yy[1], uv[0], uv[1]);
+        float* o = out + (((size_t)b * H + y) * W + x) * 3;
+        o[0] = u8_norm(p0.r); o[1] = u8_norm(p0.g); o[2] = u8_norm(p0.b);
+        o[3] = u8_norm(p1.r); o[4] = u8_norm(p1.g); o[5] = u8_norm(p1.b);
+    }
+}
+HP3D_KERNEL(256)
+void nv12_to_rgb_kernel(const Nv12Src P, int B, int H, int W, unsigned char* out) {
+    const int W2 = W / 2;
+    const long total = (long)B * H * W2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W2) * 2;
+        long r = i / W2;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const size_t fb = (size_t)b * P.frame_stride;
+        unsigned char yy[2], uv[2];
+        __builtin_memcpy(yy, P.y + fb + (size_t)y * P.pitch + x, 2);
+        __builtin_memcpy(uv, P.uv + fb + (size_t)(y >> 1) * P.pitch + x, 2);
+        const Rgb8 p0 = nv12_convert(P, yy[0], uv[0], uv[1]), p1 = nv12_convert(P, yy[1], uv[0], uv[1]);
+        unsigned char* o = out + (((size_t)b * H + y) * W + x) * 3;
+        o[0] = (unsigned char)p0.r; o[1] = (unsigned char)p0.g; o[2] = (unsigned char)p0.b;
+        o[3] = (unsigned char)p1.r; o[4] = (unsigned char)p1.g; o[5] = (unsigned char)p1.b;
+    }
+}
+
 // A detection-frame box (centre_d, crop_size_d) in frame coordinates: centre = centre_d * f + (f - 1) / 2 (the centre of detection pixel
 // p covers frame pixels p f ... p f + f - 1), crop_size = crop_size_d * f, scale from it as mask_grow_epilogue derives it (NumPy's NaN
 // rules: oracle.general.scale_from_crop_size).  Element by element: may run in place.
@@ -1732,13 +1892,17 @@ __device__ __forceinline__ void crop_and_resize_idx_body(const Tap tap, int m, i
         const int ty0 = (int)floorf(in_y), ty1 = (int)ceilf(in_y);
         const int tx0 = (int)floorf(in_x), tx1 = (int)ceilf(in_x);
         const float ly = in_y - (float)ty0, lx = in_x - (float)tx0;
-        const size_t ib = (size_t)(b / K) * H * W;
-        for (int c = 0; c < C; ++c) {
-            const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
-            const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
-            const float top = tl + (tr - tl) * lx;
-            const float bot = bl + (br - bl) * lx;
-            o[c] = top + (bot - top) * ly;
+        if constexpr (Tap::PIXEL) {
+            crop_pixel_taps(tap, (size_t)(b / K), ty0, ty1, tx0, tx1, ly, lx, o);
+        } else {
+            const size_t ib = (size_t)(b / K) * H * W;
+            for (int c = 0; c < C; ++c) {
+                const float tl = tap(ib + (size_t)ty0 * W + tx0, c), tr = tap(ib + (size_t)ty0 * W + tx1, c);
+                const float bl = tap(ib + (size_t)ty1 * W + tx0, c), br = tap(ib + (size_t)ty1 * W + tx1, c);
+                const float top = tl + (tr - tl) * lx;
+                const float bot = bl + (br - bl) * lx;
+                o[c] = top + (bot - top) * ly;
+            }
         }
     }
 }
@@ -1751,6 +1915,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_idx_u8_kernel(const unsigned char* img, int m, int H, int W, const float* center, const float* scale, const int* idx,
                                    int K, int crop, float* out) {
     crop_and_resize_idx_body(TapU8{img, 3}, m, H, W, 3, center, scale, idx, K, crop, out);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_idx_nv12_kernel(const Nv12Src src, int m, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                     int crop, float* out) {
+    crop_and_resize_idx_body(TapNv12{src}, m, H, W, 3, center, scale, idx, K, crop, out);
 }
 
 // hand_side / centre / scale of the m slots as dense arrays for the lifting stage and kp_detect: latency only
@@ -2212,6 +2381,59 @@ void downscale_launch(const float* img, int B, int H, int W, int f, float* out, 
 }
 void downscale_u8_launch(const unsigned char* img, int B, int H, int W, int f, float* out, hipStream_t s) {
     downscale_dispatch(downscale_u8_kernel<0>, downscale_u8_kernel<2>, downscale_u8_kernel<4>, downscale_u8_kernel<8>, img, B, H, W, f, out, s, B);
+}
+// ---- NV12 frames ----
+int nv12_matrix_index(const char* name) {
+    static const char* names[] = {"bt709", "bt601", "bt709_full", "bt601_full"};
+    for (int i = 0; i < 4; ++i)
+        if (!strcmp(name, names[i])) return i;
+    return -1;
+}
+Nv12Src nv12_src(const unsigned char* y, const unsigned char* uv, int pitch, size_t frame_stride, int matrix) {
+    // {ky, yoff, R's cv, G's cu, G's cv, B's cu}: the rounded coefficients ARE the definition (include/hp3d.h)
+    static const int coef[4][6] = {{298, 16, 459, -55, -136, 541}, {298, 16, 409, -100, -208, 516}, {256, 0, 403, -48, -120, 475},
+                                   {256, 0, 359, -88, -183, 454}};
+    const int* c = coef[matrix >= 0 && matrix < 4 ? matrix : 0];
+    return Nv12Src{y, uv, pitch, frame_stride, c[0], c[1], c[2], c[3], c[4], c[5]};
+}
+void nv12_to_rgb_launch(const Nv12Src& src, int B, int H, int W, unsigned char* out, hipStream_t s) {
+    HP3D_LAUNCH(nv12_to_rgb_kernel, dim3(grid_for((long)B * H * (W / 2))), dim3(256), 0, s, src, B, H, W, out);
+}
+void crop_and_resize_nv12_launch(const Nv12Src& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                 int crop, float* out, hipStream_t s) {
+    if (n < 1) return;
+    const dim3 grid(grid_for((long)n * crop * crop)), block(256);
+    if (idx) HP3D_LAUNCH(crop_and_resize_idx_nv12_kernel, grid, block, 0, s, src, n, H, W, center, scale, idx, K, crop, out);
+    else HP3D_LAUNCH(crop_and_resize_nv12_kernel, grid, block, 0, s, src, n, H, W, center, scale, crop, out, K);
+}
+void downscale_nv12_launch(const Nv12Src& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s) {
+    if (frames < 1) return;
+    if (f == 1) {
+        const dim3 grid(grid_for((long)frames * H * (W / 2))), block(256);
+        if (idx) HP3D_LAUNCH(preprocess_nv12_kernel<true>, grid, block, 0, s, src, idx, frames, H, W, out);
+        else HP3D_LAUNCH(preprocess_nv12_kernel<false>, grid, block, 0, s, src, idx, frames, H, W, out);
+        return;
+    }
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    // wide: every window row of both planes starts on an f-byte boundary (the stride only counts where a second frame is reached).
+    // It is decided on the device addresses, so nothing a caller sees says which path ran, and both give the same bits.  A tight
+    // upload of one surface (hp3d_downscale_nv12) puts the chroma plane at y + stride (B - 1) + pitch (H - 1) + W: an unused row
+    // between the planes or an odd span sends such a call down the element path whatever the pitch is.
+    const bool one = frames == 1 && !idx;
+    const int wide = (f == 2 || f == 4 || f == 8) && (uintptr_t)src.y % f == 0 && (uintptr_t)src.uv % f == 0 && src.pitch % f == 0 &&
+                     (one || src.frame_stride % f == 0) ? 1 : 0;
+    const dim3 grid(grid_for((long)frames * Hd * Wd)), block(256);
+    if (idx) {
+        if (f == 2) HP3D_LAUNCH(downscale_nv12_idx_kernel<2>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, wide, out);
+        else if (f == 4) HP3D_LAUNCH(downscale_nv12_idx_kernel<4>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, wide, out);
+        else if (f == 8) HP3D_LAUNCH(downscale_nv12_idx_kernel<8>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, wide, out);
+        else HP3D_LAUNCH(downscale_nv12_idx_kernel<0>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, 0, out);
+    } else {
+        if (f == 2) HP3D_LAUNCH(downscale_nv12_kernel<2>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, wide, out);
+        else if (f == 4) HP3D_LAUNCH(downscale_nv12_kernel<4>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, wide, out);
+        else if (f == 8) HP3D_LAUNCH(downscale_nv12_kernel<8>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, wide, out);
+        else HP3D_LAUNCH(downscale_nv12_kernel<0>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, 0, out);
+    }
 }
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s) {

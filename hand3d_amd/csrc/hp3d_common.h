@@ -526,6 +526,25 @@ void track_hands_box_pos_launch(const double* kp_image, const float* sm, int cs,
                                 int use_min_score, const int* pos, const float* box_center, const float* box_scale, float* center,
                                 float* scale, float* confidence, int* lost, int* keep_next, int* detected0, int* area0, int* claimed0,
                                 hipStream_t s);
+// NV12 frames (the layout and the colour rule: include/hp3d.h).  Nv12Src = frame 0's planes, the row pitch and the frame
+// stride in bytes, and the matrix as its integer coefficients (nv12_src; matrix = nv12_matrix_index's 0 ... 3); passed to the kernels by
+// value.  The crop (idx null: box i of n = frames * K boxes, K per frame; else box idx[i] of m = n, frame idx[i] / K), the detection frame
+// of `frames` frames (idx null: frames 0 ...; else idx[i]; f = 1: the normalised frame) and the uint8 RGB frame -- each bit-equal to its
+// uint8 kernel on the converted frame.
+struct Nv12Src {
+    const unsigned char* y;
+    const unsigned char* uv;
+    int pitch;
+    size_t frame_stride;
+    int ky, yoff, rv, gu, gv, bu;
+    Nv12Src at(int b) const { Nv12Src o = *this; o.y += (size_t)b * frame_stride; o.uv += (size_t)b * frame_stride; return o; }
+};
+int nv12_matrix_index(const char* name);          // -1: unknown
+Nv12Src nv12_src(const unsigned char* y, const unsigned char* uv, int pitch, size_t frame_stride, int matrix);
+void nv12_to_rgb_launch(const Nv12Src& src, int B, int H, int W, unsigned char* out, hipStream_t s);
+void crop_and_resize_nv12_launch(const Nv12Src& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                 int crop, float* out, hipStream_t s);
+void downscale_nv12_launch(const Nv12Src& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

@@ -165,7 +165,25 @@ class ColorHandPose3DNetwork(object):
         if detect_scale is not None:
             self.engine.set_option('detect_scale', str(int(detect_scale)))
 
-    def track(self, image, hand_side, detect_scale=None, partial_detect=None):
+    def _nv12_matrix(self, nv12_matrix):
+        if nv12_matrix is not None:
+            self.engine.set_option('nv12_matrix', str(nv12_matrix))
+
+    @staticmethod
+    def _nv12_planes(image):
+        """(y, uv) if `image` is a pair of NV12 planes, None if it is a packed frame.  A tuple always means planes; a list does only
+        where it holds two uint8 arrays [B,H,pitch] and [B,H/2,pitch] (any other list is a nested packed frame, as it always was)."""
+        if not isinstance(image, (tuple, list)):
+            return None
+        pair = len(image) == 2 and all(isinstance(p, np.ndarray) and p.dtype == np.uint8 and p.ndim == 3 for p in image)
+        if pair and image[0].shape[0] == image[1].shape[0] and image[0].shape[1] == 2 * image[1].shape[1] and image[0].shape[2] == image[1].shape[2]:
+            return image[0], image[1]
+        if isinstance(image, tuple):
+            raise ValueError("image=(y, uv): NV12 planes are two uint8 arrays [B,H,pitch] and [B,H/2,pitch]; got %s"
+                             % ", ".join(str(getattr(p, 'shape', type(p).__name__)) for p in image))
+        return None
+
+    def track(self, image, hand_side, detect_scale=None, partial_detect=None, nv12_matrix=None):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
             HandSegNet as inference() does; every other call crops with the box the dataset readers' hand_crop rule
@@ -178,12 +196,22 @@ class ColorHandPose3DNetwork(object):
             hand on the frame's f x f area mean and crops from the frame itself; the outputs keep their shapes.
             `partial_detect` = True / False sets the engine option "track_partial_detect", which stays set (None: as it is): a step
             that detects because some frames of the batch lost their hand runs HandSegNet on those frames only; the others keep
-            their tracked box and come out bit-equal to a step without the option. """
+            their tracked box and come out bit-equal to a step without the option.
+            `image` = (y, uv), a tuple or a list of the two arrays: NV12 frames as a decoder delivers them, uint8 planes [B,H,W] and
+            [B,H/2,W]; a tuple that is no such pair raises ValueError.  The crop
+            and the detection frame come straight from the planes; every output equals the call on the uint8 frame
+            hand3d_amd.utils.nv12.nv12_to_rgb makes of them, bit for bit.  `nv12_matrix` = 'bt709' | 'bt601' | 'bt709_full' |
+            'bt601_full' sets the engine option of that name, which stays set (None: as it is; a fresh engine has 'bt709'). """
         self._detect_scale(detect_scale)
+        self._nv12_matrix(nv12_matrix)
         if partial_detect is not None:
             self.engine.set_option('track_partial_detect', '1' if partial_detect else '0')
-        step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
-        o = step(image, hand_side)
+        planes = self._nv12_planes(image)
+        if planes is not None:
+            o = self.engine.track_step_nv12(planes[0], planes[1], hand_side)
+        else:
+            step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
+            o = step(image, hand_side)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],
                 o['detected'])
 
@@ -191,7 +219,7 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
-    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None):
+    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None, nv12_matrix=None):
         """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
             keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
             A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
@@ -202,11 +230,17 @@ class ColorHandPose3DNetwork(object):
             object where detected = 1).  The engine's `claimed` counters (objects a kept slot claimed on a detect step) are not in the
             tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track().
             `compact`: as for inference_hands() -- a slot with valid = 0 costs nothing behind its box and returns zeros there and
-            confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags. """
+            confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags.
+            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track(). """
         self._detect_scale(detect_scale)
         self._compact(compact)
-        step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step
-        o = step(image, hand_side, max_hands)
+        self._nv12_matrix(nv12_matrix)
+        planes = self._nv12_planes(image)
+        if planes is not None:
+            o = self.engine.track_hands_step_nv12(planes[0], planes[1], hand_side, max_hands)
+        else:
+            step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step
+            o = step(image, hand_side, max_hands)
         return (o['coord3d'], o['kp_hw'], o['kp_crop'].astype(np.float64), o['scale'], o['center'], o['confidence'], o['lost'],
                 o['detected'], o['valid'], o['area'])
 

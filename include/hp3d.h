@@ -164,6 +164,8 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            hp3d_infer_full*, hp3d_infer_2d* and hp3d_infer_hands* IGNORE the option (their score-map and mask outputs
  *                            have the frame's size).  A change between two steps counts as a change of shape: the next step detects.
  *                            The default and which f still finds a hand are policy, not measurement;
+ *          "nv12_matrix"  = "bt709" (default) | "bt601" | "bt709_full" | "bt601_full": the colour matrix of the NV12 entry points; see
+ *                            "NV12 frames" below.  Anything else: HP3D_ERR_ARG.  Every other call ignores it;
  *          "hands_min_area" = "0" (default: off) | N: hp3d_infer_hands* / hp3d_masks_from_scoremap drop objects of fewer than N pixels
  *                            instead of reporting them as hands.  A useful value depends on the trained weights: callers calibrate it on
  *                            the `area` every call returns;
@@ -505,6 +507,71 @@ int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8
 int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
                          const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
                          float* confidence, int32_t* lost);
+
+/* ---- NV12 frames (option "nv12_matrix") -----------------------------------------
+ * A third frame type of the two trackers next to float32 and uint8 [B,H,W,3]: what a hardware decoder, a camera or a capture card
+ * delivers.  Every NV12 entry point is DEFINED as bit-equal to its uint8 entry point on the frame hp3d_nv12_to_rgb makes.
+ * Layout.  y points at frame 0's luma: H rows of `pitch` bytes, the first W of each row used.  uv points at frame 0's chroma: H/2 rows of
+ *   the same pitch, U at even bytes and V at odd bytes, the first W bytes of each row used.  Frame b lies at y + b frame_stride and
+ *   uv + b frame_stride (bytes).  H and W are even and at least 16 (and what every frame must satisfy); pitch >= W; B = 1 (frame_stride is
+ *   then ignored) or frame_stride >= pitch (H - 1) + W.  ONLY bytes [r pitch, r pitch + W) of a row are ever read: the padding may be
+ *   unmapped.
+ * Pixel (r, c):  Y = y[r pitch + c],  U = uv[(r >> 1) pitch + (c & ~1)],  V = uv[(r >> 1) pitch + (c | 1)].  Chroma is REPLICATED over its
+ *   2 x 2 block and not interpolated: that is the rule.
+ * Conversion, exact integer arithmetic: with int32 C = Y - yoff, D = U - 128, E = V - 128 each channel is
+ *   clamp((ky C + cu D + cv E + 128) >> 8, 0, 255), the shift arithmetic (floor):
+ *     "nv12_matrix"          ky, yoff    R (cu, cv)   G (cu, cv)     B (cu, cv)
+ *     "bt709" (default)      298, 16     0, 459       -55, -136      541, 0
+ *     "bt601"                298, 16     0, 409       -100, -208     516, 0
+ *     "bt709_full"           256, 0      0, 403       -48, -120      475, 0
+ *     "bt601_full"           256, 0      0, 359       -88, -183      454, 0
+ *   The default is bt709 because the feature is about HD video: a policy choice, not a measurement.  The rounded coefficients ARE the
+ *   definition: no decoder promises these bits.  A uint8 channel becomes a network value as the uint8 path makes it: float(ch) / 255 -
+ *   0.5, float32 op by op.
+ * hp3d_track_step_nv12 / hp3d_track_hands_step_nv12   the planes on the host; the call uploads them (1.5 bytes a pixel; packed tight on
+ *   the way).  Outputs, state and options as hp3d_track_step_u8 / hp3d_track_hands_step_u8 on the converted frames, bit for bit:
+ *   "detect_scale", "track_partial_detect", "hands_compact", "track_redetect", half-precision trunks and micro-batch chunks included.
+ * hp3d_track_step_nv12_dev / hp3d_track_hands_step_nv12_dev   y / uv are device pointers: the caller's surfaces are read in place,
+ *   stream-ordered like hp3d_track_step_dev; every other pointer is a device pointer too.
+ * What a step launches on the frame.  A TRACKED step: one crop per chunk, straight from the two planes (four conversions per output
+ *   pixel; profile row "crop_and_resize_nv12", with "hands_compact" "crop_and_resize_idx_nv12"; counter "crop_nv12_launches") -- the RGB
+ *   frame never exists at any size.  A DETECT step at "detect_scale" f > 1: the detection frame straight from the planes (every luma pixel
+ *   of a window is converted, the three integer sums are exact; rows "downscale_nv12" / "downscale_nv12_idx"), then that crop.  A DETECT
+ *   step at f = 1: the normalised float32 frame with one launch ("preprocess_nv12"; a partial detect step: the m lost frames only,
+ *   "preprocess_nv12_idx"), detection and crop from it as the uint8 form does.
+ * Errors, each HP3D_ERR_ARG before any launch with a message that names the argument: odd H or W, pitch < W, y or uv NULL, a
+ *   frame_stride below pitch (H - 1) + W at B > 1; an unknown "nv12_matrix" is refused by hp3d_set_option.
+ * Out of scope: the single-picture calls (hp3d_infer_full*, hp3d_infer_hands*) get no NV12 form; hp3d_nv12_to_rgb plus their _u8 forms
+ *   serve a one-off picture.
+ * The per-op forms (host pointers; the kernels run on the pitch and stride given):
+ * hp3d_nv12_to_rgb            -> out [B,H,W,3] uint8 (the rule above)
+ * hp3d_crop_and_resize_nv12   center [B K,2], scale [B K], K boxes per frame; idx NULL: all B K boxes -> out [B K,crop,crop,3] (m ignored);
+ *                             else idx [m] slot indices in [0, B K), 0 <= m <= B K -> out [m,crop,crop,3] (crop i = box idx[i] of frame
+ *                             idx[i] / K).  = hp3d_crop_and_resize_u8 / hp3d_crop_and_resize_idx on the converted frames, bit for bit
+ * hp3d_downscale_nv12         f in 1 ... 8 (f = 1: the normalised frame = hp3d_preprocess_u8 at equal sizes); idx NULL: all B frames;
+ *                             else idx [m] frames in [0, B), 1 <= m <= B -> out [B or m,ceil(H/f),ceil(W/f),3].  = hp3d_downscale_u8 on the
+ *                             converted frames, bit for bit                                                                        */
+int hp3d_track_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                         const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                         float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                         int32_t* detected);
+int hp3d_track_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                             const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                             float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                             int32_t* detected);
+int hp3d_track_hands_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride, int K,
+                               const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                               float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                               int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_track_hands_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
+                                   int K, const float* hand_side, float* image_crop, float* scale_crop, float* center,
+                                   float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw,
+                                   float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_nv12_to_rgb(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, uint8_t* out);
+int hp3d_crop_and_resize_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, int K,
+                              const float* center, const float* scale, const int32_t* idx, int m, int crop_size, float* out);
+int hp3d_downscale_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, int f,
+                        const int32_t* idx, int m, float* out);
 
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65

@@ -5,7 +5,10 @@ a tracked step is the same run's full-path time minus its event-timed HandSegNet
 step would cost if skipping were free.  Tracked steps are timed twice: as a video runs them (seeded once, then step after step;
 valid only if the counters say that every timed step was a tracked one -- with random weights a step may lose the hand) and with
 hp3d_track_seed in front of every step (always tracked; the seed's two uploads and stream synchronise are timed on their own as
-well).  Writes one JSON line to profiles/track_bench.json."""
+well).
+Also NV12 frames at B = 1, 1080x1920 against the uint8 and float32 forms of the same run: host-frame tracked
+steps, device-frame tracked steps, and the frame-reading rows of a detect step at detect_scale = 4.
+Writes one JSON line to profiles/track_bench.json."""
 import argparse
 import ctypes as C
 import json
@@ -20,7 +23,8 @@ sys.path.insert(0, ROOT)
 from hand3d_amd import _lib, synth      # noqa: E402
 
 
-def median3(fn, steps, sync):
+def regions3(fn, steps, sync):
+    """ms per call of three timed regions, ascending."""
     ts = []
     for _ in range(3):
         sync()
@@ -29,7 +33,16 @@ def median3(fn, steps, sync):
             fn()
         sync()
         ts.append((time.perf_counter() - t0) / steps * 1e3)
-    return sorted(ts)[1]
+    return sorted(ts)
+
+
+def median3(fn, steps, sync):
+    return regions3(fn, steps, sync)[1]
+
+
+def spread3(fn, steps, sync):
+    """[min, median, max] of three timed regions, ms per call: the spread is what a difference between two medians has to exceed."""
+    return [round(t, 4) for t in regions3(fn, steps, sync)]
 
 
 def case(e, B, H, W, steps, warmup):
@@ -110,6 +123,82 @@ def host_u8_case(e, H, W, steps, warmup):
             'tracked_f32_host_ms': median3(tracked_f32, steps, e.sync)}
 
 
+def nv12_case(e, H, W, steps, warmup):
+    """B = 1 at H x W: the NV12 entry points against the uint8 / float32 ones in the same run.  The planes are the synth frame pushed
+    through hand3d_amd.utils.nv12.rgb_to_nv12; the uint8 frame is nv12_to_rgb of them, so both sides see the same picture."""
+    from hand3d_amd.utils.nv12 import nv12_to_rgb, rgb_to_nv12
+    img = synth.make_batch(3, 1, H, W)
+    y, uv = rgb_to_nv12(np.clip(np.rint((img + 0.5) * 255.0), 0, 255).astype(np.uint8))
+    u8 = nv12_to_rgb(y, uv)
+    f32 = (u8.astype(np.float32) / np.float32(255.0) - np.float32(0.5)).astype(np.float32)
+    hs = synth.hand_sides(1)
+    o = e.infer_full(f32, hs, outputs=('scale', 'center'))
+    kpc, kph, c3 = np.empty((1, 21, 2), np.int32), np.empty((1, 21, 2), np.float64), np.empty((1, 21, 3), np.float32)
+    lost, det, conf = np.empty(1, np.int32), np.empty(1, np.int32), np.empty(1, np.float32)
+    p = _lib._ptr
+    seed = lambda: e.track_seed(o['center'], o['scale'], H, W)
+
+    def host_u8():
+        seed()
+        e._chk(e.lib.hp3d_track_step_u8(e.h, 1, H, W, p(u8), H, W, p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+
+    def host_nv12():
+        seed()
+        e._chk(e.lib.hp3d_track_step_nv12(e.h, 1, H, W, p(y), p(uv), W, 0, p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+    surf = np.concatenate([y, uv], axis=1)
+    d_f32, d_surf, d_hs = e.to_device(f32), e.to_device(surf), e.to_device(hs)
+    out = {k: e.dev_alloc(n) for k, n in (('coord3d', 63 * 4), ('kp_hw', 42 * 8), ('kp_crop', 42 * 4), ('center', 8), ('scale', 4),
+                                          ('confidence', 4), ('lost', 4), ('detected', 4))}
+    outs = {k: int(v) for k, v in out.items()}
+
+    def dev_f32():
+        seed()
+        e.track_step_dev(1, H, W, d_f32, d_hs, **outs)
+
+    def dev_nv12():
+        seed()
+        e.track_step_nv12_dev(1, H, W, int(d_surf), int(d_surf) + H * W, W, 0, d_hs, **outs)
+    for _ in range(warmup):
+        host_u8(); host_nv12(); dev_f32(); dev_nv12()
+    n0 = e.counter('track_tracked_steps')
+    r = {'H': H, 'W': W, 'regions': '[min, median, max] ms of three',
+         'tracked_u8_host_ms': spread3(host_u8, steps, e.sync), 'tracked_nv12_host_ms': spread3(host_nv12, steps, e.sync),
+         'tracked_f32_dev_ms': spread3(dev_f32, steps, e.sync), 'tracked_nv12_dev_ms': spread3(dev_nv12, steps, e.sync)}
+    assert e.counter('track_tracked_steps') - n0 == 12 * steps, "a timed step was not a tracked one"
+    # the frame-reading rows, event-timed: a tracked step's crop, and a detect step's detection frame + crop at detect_scale = 4.  One
+    # pass unrecorded (caches, code objects), then [min, median, max] of three per row
+    def rows():
+        return {name: ms for name, _, ms, _, _ in e.profile() if name.startswith(('crop_and_resize', 'downscale', 'preprocess'))}
+
+    def rows3(calls):
+        got = {k: [] for k in calls}
+        for i in range(4):
+            for k, fn in calls.items():
+                fn()
+                e.sync()
+                if i:
+                    got[k].append(rows())
+        return {k: {name: [round(t, 4) for t in sorted(p[name] for p in v)] for name in v[0]} for k, v in got.items()}
+
+    def detect(nv12):
+        e.track_reset()
+        if nv12:
+            e._chk(e.lib.hp3d_track_step_nv12(e.h, 1, H, W, p(y), p(uv), W, 0, p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+        else:
+            e._chk(e.lib.hp3d_track_step_u8(e.h, 1, H, W, p(u8), H, W, p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det)))
+    e.set_profiling(1)
+    r.update(rows3({'tracked_u8_rows_ms': host_u8, 'tracked_nv12_rows_ms': host_nv12, 'tracked_f32_dev_rows_ms': dev_f32,
+                    'tracked_nv12_dev_rows_ms': dev_nv12}))
+    e.set_option('detect_scale', '4')
+    r.update(rows3({'detect_f4_u8_rows_ms': lambda: detect(False), 'detect_f4_nv12_rows_ms': lambda: detect(True)}))
+    e.set_profiling(0)
+    e.set_option('detect_scale', '1')
+    e.track_reset()
+    for b in list(out.values()) + [d_f32, d_surf, d_hs]:
+        b.free()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -122,7 +211,8 @@ def main():
     res = {'bench': 'track', 'steps': a.steps, 'warmup': a.warmup,
            'cases': [case(e, 1, 240, 320, a.steps, a.warmup), case(e, 1, 1080, 1920, max(a.steps // 2, 5), a.warmup),
                      case(e, 32, 320, 320, max(a.steps // 2, 5), max(a.warmup // 2, 2))],
-           'host_u8_1080p': host_u8_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup)}
+           'host_u8_1080p': host_u8_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup),
+           'nv12_1080p': nv12_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup)}
     e.close()
     line = json.dumps(res)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
