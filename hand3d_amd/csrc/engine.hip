@@ -324,15 +324,26 @@ struct Counters {
     long crop_nv12_launches = 0;                    // crops taken straight from an NV12 frame (either crop_and_resize*_nv12_kernel)
 };
 
-// Option "hands_compact" (DESIGN.md 4.15).  h_map: two page-locked buffers used in turn, idx [cap] | pos [cap] of one chunk; a buffer is
+// A page-locked int buffer that small copies fill or drain behind the stream (the trackers' flags, the compaction's maps), the event
+// behind the last of them and whether it has been waited for.  The host touches h only after wait().
+struct HostFlags {
+    int* h = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    int resize(hp3d_ctx* ctx, size_t n, const char* what);          // n ints, contents undefined; the caller has waited
+    int wait(hp3d_ctx* ctx);
+    int record(hp3d_ctx* ctx);                    // a copy that reads or writes h has just been enqueued
+    int copy_behind(hp3d_ctx* ctx, const int* d_src, size_t n);      // h <- n ints of the device, behind the stream
+    void free();
+};
+
+// Option "hands_compact" (DESIGN.md 4.15).  map: two page-locked buffers used in turn, idx [cap] | pos [cap] of one chunk; a buffer is
 // rewritten only after the event behind its last upload.  d_map: the same on the device (stream order protects it).
 struct CompactBufs {
     int cap = 0;                        // slots the buffers hold
-    int* h_map[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool busy[2] = {false, false};
+    HostFlags map[2];
     int turn = 0;
-    int* h_valid = nullptr;             // page-locked: a chunk's valid flags (detect steps, hp3d_infer_hands*)
+    HostFlags valid;                    // a chunk's valid flags (detect steps, hp3d_infer_hands*)
     int* d_map = nullptr;
     float *d_hs = nullptr, *d_center = nullptr, *d_scale = nullptr;      // hand_side / centre / scale of the slots that run, dense
 };
@@ -347,9 +358,7 @@ struct TrackState {
     float* conf = nullptr;
     int *lost = nullptr, *detected = nullptr;
     int *pidx = nullptr, *ppos = nullptr;      // option "track_partial_detect": per chunk at its offset, the lost frames' indices in the chunk | a frame's dense index
-    int* h_lost = nullptr;              // page-locked: the last step's flags (copied behind the step, ev_lost)
-    hipEvent_t ev_lost = nullptr;
-    bool pending = false;               // that copy has been enqueued and not waited for yet
+    HostFlags h_lost;                   // the last step's flags, copied behind the step
     int cur = 0;
     bool valid = false;                 // box[cur] holds boxes for (B, H, W)
     int B = 0, H = 0, W = 0;
@@ -366,9 +375,7 @@ struct TrackHandsState {
     float* conf = nullptr;
     int *flags = nullptr, *detected = nullptr, *area = nullptr, *claimed = nullptr;
     int* keep = nullptr;                // valid and not lost after the last step: what a detect step behind it keeps
-    int* h_flags = nullptr;             // page-locked: the last step's valid | lost (copied behind the step, ev_flags)
-    hipEvent_t ev_flags = nullptr;
-    bool pending = false;
+    HostFlags h_flags;                  // the last step's valid | lost, copied behind the step
     int cur = 0;
     bool ok = false;                    // box[cur] and the flags hold a state for (B, K, H, W)
     int B = 0, K = 0, H = 0, W = 0;
@@ -494,6 +501,59 @@ struct ProfScope {          // kernel == nullptr: no profile row
 void prof_reset(hp3d_ctx* ctx) {
     ctx->prof.clear();
     ctx->event_next = 0;
+}
+
+// One call = one profile, whatever the number of its chunks: mode 1 starts the call with an empty profile and lets the later chunks
+// accumulate like mode 2 (which accumulates across calls); the caller's mode is back on every exit.
+struct ProfCall {
+    hp3d_ctx* ctx;
+    const int saved;
+    explicit ProfCall(hp3d_ctx* c) : ctx(c), saved(c->profiling) {
+        if (saved != 2) prof_reset(c);
+    }
+    void chunk(int b0) {
+        if (b0 > 0 && saved == 1) ctx->profiling = 2;
+    }
+    ~ProfCall() { ctx->profiling = saved; }
+};
+
+#ifdef HP3D_EMU          // the CPU interpreter has neither page-locked memory nor event flags
+int* host_ints_alloc(size_t n) { return (int*)malloc(sizeof(int) * n); }
+void host_ints_free(int* p) { free(p); }
+hipError_t flag_event_create(hipEvent_t* e) { return hipEventCreate(e); }
+#else
+int* host_ints_alloc(size_t n) {
+    int* p = nullptr;
+    return hipHostMalloc((void**)&p, sizeof(int) * n, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+void host_ints_free(int* p) { hipHostFree(p); }
+hipError_t flag_event_create(hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
+#endif
+
+int HostFlags::resize(hp3d_ctx* ctx, size_t n, const char* what) {
+    if (h) host_ints_free(h);
+    h = host_ints_alloc(n);
+    if (!h) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "%s: host allocation failed", what);
+    if (!ev) HIPCHK(ctx, flag_event_create(&ev));
+    return 0;
+}
+int HostFlags::wait(hp3d_ctx* ctx) {
+    if (pending) { HIPCHK(ctx, hipEventSynchronize(ev)); pending = false; }
+    return 0;
+}
+int HostFlags::record(hp3d_ctx* ctx) {
+    HIPCHK(ctx, hipEventRecord(ev, ctx->stream));
+    pending = true;
+    return 0;
+}
+int HostFlags::copy_behind(hp3d_ctx* ctx, const int* d_src, size_t n) {
+    HIPCHK(ctx, hipMemcpyAsync(h, d_src, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+    return record(ctx);
+}
+void HostFlags::free() {
+    if (h) host_ints_free(h);
+    if (ev) hipEventDestroy(ev);
+    *this = HostFlags();
 }
 
 // ---- weight packing ------------------------------------------------------------------------
@@ -1752,7 +1812,7 @@ int finish_op(hp3d_ctx* ctx) {
 int ensure_track(hp3d_ctx* ctx, int B) {
     TrackState& T = ctx->track;
     if (B <= T.cap) return 0;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }
+    CHK(T.h_lost.wait(ctx));
     for (int i = 0; i < 2; ++i) {
         CHK(dev_realloc(ctx, &T.center[i], (size_t)B * 2));
         CHK(dev_realloc(ctx, &T.scale[i], (size_t)B));
@@ -1762,17 +1822,7 @@ int ensure_track(hp3d_ctx* ctx, int B) {
     CHK(dev_realloc(ctx, &T.detected, (size_t)B));
     CHK(dev_realloc(ctx, &T.pidx, (size_t)B));
     CHK(dev_realloc(ctx, &T.ppos, (size_t)B));
-#ifdef HP3D_EMU
-    free(T.h_lost);
-    T.h_lost = (int*)malloc(sizeof(int) * (size_t)B);
-    if (!T.ev_lost) HIPCHK(ctx, hipEventCreate(&T.ev_lost));
-#else
-    if (T.h_lost) HIPCHK(ctx, hipHostFree(T.h_lost));
-    T.h_lost = nullptr;
-    HIPCHK(ctx, hipHostMalloc((void**)&T.h_lost, sizeof(int) * (size_t)B, hipHostMallocDefault));
-    if (!T.ev_lost) HIPCHK(ctx, hipEventCreateWithFlags(&T.ev_lost, hipEventDisableTiming));
-#endif
-    if (!T.h_lost) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "tracking state: host allocation failed");
+    CHK(T.h_lost.resize(ctx, (size_t)B, "tracking state"));
     T.cap = B;
     T.valid = false;
     return 0;
@@ -1789,12 +1839,7 @@ void track_free(hp3d_ctx* ctx) {
     if (T.detected) hipFree(T.detected);
     if (T.pidx) hipFree(T.pidx);
     if (T.ppos) hipFree(T.ppos);
-#ifdef HP3D_EMU
-    free(T.h_lost);
-#else
-    if (T.h_lost) hipHostFree(T.h_lost);
-#endif
-    if (T.ev_lost) hipEventDestroy(T.ev_lost);
+    T.h_lost.free();
     T = TrackState();
 }
 
@@ -1959,6 +2004,148 @@ int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W,
     return 0;
 }
 
+// ---- what the step functions share (hp3d_track_step*, hp3d_track_hands_step*, hp3d_infer_hands*) ----------------------------------
+// What a step was handed: the frames -- float32, uint8 (host) or NV12, exactly one is set -- and hand_side; dev: device pointers.
+struct StepIn {
+    const float* image = nullptr;
+    const unsigned char* image_u8 = nullptr;
+    const Nv12Arg* nv = nullptr;
+    const float* hand_side = nullptr;
+    bool dev = false;
+    bool raw() const { return image_u8 || nv; }          // uint8 or NV12 frames: no float32 frame comes in
+};
+// Where a step's results go, one entry per slot (null: skipped); device pointers when the step's input is.
+struct StepOut {
+    float *image_crop = nullptr, *scale_crop = nullptr, *center = nullptr, *kp_scoremap = nullptr, *coord3d = nullptr;
+    int32_t* kp_crop = nullptr;
+    double* kp_image = nullptr;
+    float* confidence = nullptr;
+    int32_t *lost = nullptr, *detected = nullptr, *valid = nullptr, *area = nullptr, *claimed = nullptr;
+    // the outputs of the chunk that starts at slot s0
+    StepOut at(size_t s0) const {
+        StepOut o;
+        auto off = [s0](auto* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        o.image_crop = off(image_crop, 256 * 256 * 3); o.scale_crop = off(scale_crop, 1); o.center = off(center, 2);
+        o.kp_scoremap = off(kp_scoremap, 256 * 256 * 21); o.coord3d = off(coord3d, 63);
+        o.kp_crop = off(kp_crop, 42); o.kp_image = off(kp_image, 42); o.confidence = off(confidence, 1);
+        o.lost = off(lost, 1); o.detected = off(detected, 1); o.valid = off(valid, 1); o.area = off(area, 1); o.claimed = off(claimed, 1);
+        return o;
+    }
+};
+int copy_out(hp3d_ctx* ctx, int32_t* dst, const int* src, size_t n, bool dev) {          // (int32: four bytes each, as copy_out counts)
+    return copy_out(ctx, (float*)dst, (const float*)src, n, dev);
+}
+
+// The frames of a tracking step on the device.  upload(), once: uint8 frames into d_u8, NV12 surfaces in place (dev) or as their packed
+// upload.  chunk(), per chunk of nb frames from b0 with K slots each: hand_side and a host float32 frame to the device, then the chunk's
+// FrameSrc.  stage: the host float32 frame goes to d_stage, because the chunk puts something else into d_image (a detection frame, the
+// gathered lost frames).
+struct StepFrames {
+    const StepIn& in;
+    const int H, W;
+    Nv12Src nvs{}, nvc{};
+    const float* d_hs = nullptr;          // the chunk's hand_side on the device
+    FrameSrc src;                         // the chunk's frames (src.nv12 points into this record)
+    int upload(hp3d_ctx* ctx, int B) {
+        if (in.image_u8) {
+            const size_t nbytes = (size_t)B * H * W * 3;
+            if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, in.image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (in.nv && in.dev) nvs = nv12_src(in.nv->y, in.nv->uv, in.nv->pitch, B > 1 ? (size_t)in.nv->frame_stride : 0, ctx->nv12_matrix);
+        else if (in.nv) CHK(upload_nv12(ctx, B, H, W, *in.nv, &nvs));
+        return 0;
+    }
+    int chunk(hp3d_ctx* ctx, int b0, int nb, int K, bool stage) {
+        const size_t px = (size_t)H * W * 3;
+        d_hs = in.hand_side + (size_t)b0 * K * 2;
+        src = FrameSrc();
+        src.f32 = in.image ? in.image + b0 * px : nullptr;
+        src.u8 = in.image_u8 ? ctx->d_u8 + b0 * px : nullptr;
+        if (!in.dev) {
+            CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * K * 2, false));
+            d_hs = ctx->d_hs;
+            if (!in.raw()) {
+                float* to = stage ? ctx->d_stage : ctx->d_image;
+                CHK(copy_in(ctx, to, src.f32, nb * px, false));
+                src.f32 = to;
+            }
+        }
+        nvc = nvs.at(b0);
+        src.nv12 = in.nv ? &nvc : nullptr;
+        return 0;
+    }
+};
+
+// frames per chunk of a multi-hand call: a chunk of the front half's size that holds at most micro_batch slots (at least one frame)
+int slot_micro_batch(const hp3d_ctx* ctx, int B, int K, int H, int W) {
+    const int front = auto_micro_batch(ctx, B, H, W), back = auto_micro_batch(ctx, B * K, 256, 256);
+    int mb = front <= 0 ? B : std::min(front, B);
+    if (back > 0) mb = std::min(mb, std::max(1, back / K));
+    return mb;
+}
+
+// The boxes of a detect step's chunk: HandSegNet, the soft-max and the mask growth on the frames themselves -- a raw frame is normalised
+// into d_image first, as hp3d_infer_full_u8 does -- or, at detect_scale > 1, on their area mean (run_detect_reduced).  *crop_src: what
+// the crops are then taken from -- the frames, or the normalised frame where one was made (the crop is then infer_full_impl's).
+int run_detect_front(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W, int Hd, int Wd, int K, const MaskKeep& mk, FrameSrc* crop_src) {
+    *crop_src = src;
+    if (ctx->detect_scale > 1) return run_detect_reduced(ctx, src, nb, H, W, Hd, Wd, K, mk);
+    const bool raw = src.u8 || src.nv12;
+    if (raw) {
+        CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
+        *crop_src = FrameSrc();
+        crop_src->f32 = ctx->d_image;
+    }
+    return run_detect_and_crop(ctx, crop_src->f32, nb, H, W, 0, raw, false, K, mk);
+}
+
+// The back half of every step behind the n crops in d_crop: PoseNet2D, then the lifting stage with the heat-map up-sampling and the
+// keypoint detection beside it (on two streams with option "lift_overlap": infer_full_impl).
+struct BackHalf {
+    int n;
+    const float* hand_side;               // device, per slot
+    const float *center, *scale;          // device: the boxes kp_detect maps the keypoints with (null: d_center / d_scale)
+    float* kpmap;                         // device: where the up-sampled maps go (null: none)
+    int32_t* kp_crop;                     // kp_detect's outputs as run_kp_detect takes them
+    double* kp_image;
+    bool dev;
+    bool kp_detect;                       // the trackers: always (the next boxes come from the keypoints); hp3d_infer_hands*: when asked for
+};
+// after_kp: the caller's launches behind kp_detect (the trackers' box rule)
+template <class F>
+int run_back_half(hp3d_ctx* ctx, const BackHalf& b, F&& after_kp) {
+    CHK(run_posenet(ctx, ctx->d_crop, b.n, 256, 256, true));
+    const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
+        if (b.kpmap) {
+            ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * b.n * (32 * 32 * 21 + 256 * 256 * 21));
+            resize_bilinear_launch(ctx->d_sm[2], b.n, 32, 32, 21, 32, 256, 256, b.kpmap, st);
+        }
+        return 0;
+    };
+    const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
+        if (b.kp_detect) CHK(run_kp_detect(ctx, b.n, b.kp_crop, b.kp_image, b.dev, b.scale, b.center));
+        return after_kp();
+    };
+    return run_pose3d(ctx, ctx->d_sm[2], b.hand_side, b.n, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up);
+}
+// ... for a step whose caller reads the maps from `out` (a device caller) or from d_kpmap (a host caller: copy_out_slots)
+BackHalf back_half_to(hp3d_ctx* ctx, const StepOut& out, int n, const float* hand_side, const float* center, const float* scale, bool dev,
+                      bool kp_detect) {
+    float* kpmap = !out.kp_scoremap ? nullptr : dev ? out.kp_scoremap : ctx->d_kpmap;
+    return BackHalf{n, hand_side, center, scale, kpmap, out.kp_crop, out.kp_image, dev, kp_detect};
+}
+// image_crop, the boxes, kp_scoremap and coord3d of n slots to the caller, in infer_full_impl's order.  back = false: a compacted chunk
+// has delivered crop, maps and coordinates itself.
+int copy_out_slots(hp3d_ctx* ctx, const StepOut& out, int n, const float* scale, const float* center, bool dev, bool back = true) {
+    if (back) CHK(copy_out(ctx, out.image_crop, ctx->d_crop, (size_t)n * 256 * 256 * 3, dev));
+    CHK(copy_out(ctx, out.scale_crop, scale, (size_t)n, dev));
+    CHK(copy_out(ctx, out.center, center, (size_t)n * 2, dev));
+    if (back && !dev) CHK(copy_out(ctx, out.kp_scoremap, ctx->d_kpmap, (size_t)n * 256 * 256 * 21, false));
+    if (back) CHK(copy_out(ctx, out.coord3d, ctx->d_coord, (size_t)n * 63, dev));
+    return 0;
+}
+
 // One step of a video: a DETECT step (HandSegNet -> mask -> box for the whole batch, then per image the tracked box where it is
 // still good) or a TRACKED step (no HandSegNet, no soft-max, no mask growth: the crop comes from the boxes the previous step
 // derived from its keypoints).  Behind the crop both are infer_full_impl: PoseNet2D, the lifting stage, keypoint detection -- plus
@@ -1967,27 +2154,23 @@ int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W,
 // one kernel plan per step, no gather of the lost images -- unless option "track_partial_detect" (DESIGN.md 4.16): a detect step that
 // only `lost` flags caused then runs HandSegNet, the soft-max and the mask growth per chunk at batch m = the chunk's lost frames, on
 // those frames (0 < m < nb: "partial"; m = 0: the chunk is enqueued as a tracked chunk; m = nb: as without the option).
-// image_u8 (host, frame = network size) instead of image: the tracked step crops straight from the uint8 frame, the detect step
-// normalises it first (preprocess_u8) as hp3d_infer_full_u8 does.
-// (track_hands_step_impl below repeats this function's frame per slot: a fix to the upload, the chunk loop, the kp_up / kp_work pair or
-//  the copy_out sequence here belongs there as well.)
-int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, const unsigned char* image_u8, const float* hand_side,
-                    float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
-                    double* kp_image, float* confidence, int32_t* lost, int32_t* detected, bool dev, const Nv12Arg* nv = nullptr) {
-    if ((!image && !image_u8 && !nv) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    if (nv) CHK(check_nv12(ctx, B, H, W, *nv));
+// uint8 frames (host, frame = network size): the tracked step crops straight from the uint8 frame, the detect step normalises it
+// first (preprocess_u8) as hp3d_infer_full_u8 does.
+int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const StepIn& in, const StepOut& out) {
+    if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
     CHK(check_img(ctx, B, H, W));
-    const bool raw = image_u8 || nv;                     // uint8 or NV12 frames: no float32 frame comes in
+    const bool dev = in.dev;
     int Hd, Wd;
     CHK(detect_frame(ctx, H, W, &Hd, &Wd));
     const int f = ctx->detect_scale;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TrackState& T = ctx->track;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
+    CHK(T.h_lost.wait(ctx));                             // the only wait tracking adds: the previous step's flags
     const bool fresh = !T.valid || T.B != B || T.H != H || T.W != W || T.f != f;
     bool any_lost = false;
     if (!fresh)
-        for (int b = 0; b < B; ++b) any_lost = any_lost || T.h_lost[b] != 0;
+        for (int b = 0; b < B; ++b) any_lost = any_lost || T.h_lost.h[b] != 0;
     const bool sched = ctx->track_redetect > 0 && T.since + 1 >= ctx->track_redetect;
     const bool detect = fresh || any_lost || sched;
     const int force_all = (fresh || sched) ? 1 : 0;      // nothing to keep / a scheduled re-detection re-boxes every image
@@ -1998,51 +2181,31 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
     // option "track_partial_detect": only a detect step that `lost` flags alone caused (a fresh or scheduled one re-boxes every image)
     const bool partial_step = ctx->track_partial_detect && detect && !force_all;
     // a host float32 frame is staged where the detection frame (f > 1) or the gathered lost frames (a partial chunk) go to d_image
-    if ((f > 1 || partial_step) && !dev && !raw) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    if ((f > 1 || partial_step) && !dev && !in.raw()) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track(ctx, B));
     T.valid = false;                                     // a step that fails half way leaves no boxes behind
-    if (image_u8) {
-        const size_t nbytes = (size_t)B * H * W * 3;
-        if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    Nv12Src nvs{};                                       // NV12 frames: the caller's surfaces in place (dev) or their packed upload
-    if (nv && dev) nvs = nv12_src(nv->y, nv->uv, nv->pitch, B > 1 ? (size_t)nv->frame_stride : 0, ctx->nv12_matrix);
-    else if (nv) CHK(upload_nv12(ctx, B, H, W, *nv, &nvs));
-    const int saved_prof = ctx->profiling;
-    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
-    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    StepFrames fr{in, H, W};
+    CHK(fr.upload(ctx, B));
+    ProfCall prof(ctx);
     const int cur = T.cur, nxt = T.cur ^ 1;
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = std::min(mb, B - b0);
-        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one step = one profile: keep the earlier chunks
-        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
-        const float* d_hs = hand_side + (size_t)b0 * 2;
-        const unsigned char* d_u8 = image_u8 ? ctx->d_u8 + (size_t)b0 * H * W * 3 : nullptr;
+        prof.chunk(b0);
         int m = nb;                                      // the chunk's frames that detect
         if (partial_step) {
             m = 0;
-            for (int b = b0; b < b0 + nb; ++b) m += T.h_lost[b] != 0 ? 1 : 0;
+            for (int b = b0; b < b0 + nb; ++b) m += T.h_lost.h[b] != 0 ? 1 : 0;
         }
         const bool partial = partial_step && m > 0 && m < nb;
         const bool chunk_detect = detect && m > 0;       // (m = 0: another chunk holds the lost frame; this one runs as a tracked chunk)
-        if (!dev) {
-            CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)nb * 2, false));
-            d_hs = ctx->d_hs;
-            if (!raw) {
-                float* stage = (f > 1 || partial) ? ctx->d_stage : ctx->d_image;
-                CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
-                d_img = stage;
-            }
-        }
-        const Nv12Src nvc = nvs.at(b0);
-        FrameSrc src;
-        src.f32 = d_img; src.u8 = d_u8; src.nv12 = nv ? &nvc : nullptr;
+        CHK(fr.chunk(ctx, b0, nb, 1, f > 1 || partial));
+        const FrameSrc& src = fr.src;
+        FrameSrc crop_src = src;
         float* bc = T.center[cur] + (size_t)b0 * 2;
         float* bs = T.scale[cur] + b0;
-        int* pidx = T.pidx + b0;
-        int* ppos = T.ppos + b0;
         if (partial) {           // idx / pos from the flags, which this chunk's track_box has not overwritten yet
+            int* pidx = T.pidx + b0;
+            int* ppos = T.ppos + b0;
             {
                 ProfScope ps(ctx, "track_partial_index", "track_partial_index", 0.0, 12.0 * nb);
                 track_partial_index_launch(T.lost + b0, nb, pidx, ppos, ctx->stream);
@@ -2053,77 +2216,39 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
             if (f > 1) {
                 CHK(run_detect_reduced(ctx, src, m, H, W, Hd, Wd, 0, MaskKeep(), pidx));
             } else {
-                if (raw) {
+                if (in.raw()) {
                     CHK(normalise_frames(ctx, src, pidx, m, H, W));
                 } else {
                     ProfScope ps(ctx, "frame_gather", "frame_gather", 0.0, 8.0 * m * H * W * 3);
-                    frame_gather_launch(d_img, pidx, m, (size_t)H * W * 3, ctx->d_image, ctx->stream);
+                    frame_gather_launch(src.f32, pidx, m, (size_t)H * W * 3, ctx->d_image, ctx->stream);
                     ++ctx->frame_gather_launches;
                 }
                 HIPCHK(ctx, hipGetLastError());
                 CHK(run_detect_and_crop(ctx, ctx->d_image, m, H, W, 0, true, false));
             }
-            {
-                ProfScope ps(ctx, "track_select_pos", "track_select_pos", 0.0, 16.0 * nb);
-                track_select_pos_launch(T.lost + b0, ppos, ctx->d_center, ctx->d_scale, nb, bc, bs, T.detected + b0, ctx->stream);
-            }
-            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));          // (a raw frame: all nb crops straight from it = normalise, then crop, bit for bit)
-        } else if (chunk_detect && f > 1) {
-            CHK(run_detect_reduced(ctx, src, nb, H, W, Hd, Wd));
-            {
-                ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
-                track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
-            }
-            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));
+            ProfScope ps(ctx, "track_select_pos", "track_select_pos", 0.0, 16.0 * nb);
+            track_select_pos_launch(T.lost + b0, ppos, ctx->d_center, ctx->d_scale, nb, bc, bs, T.detected + b0, ctx->stream);
+            // (a raw frame: all nb crops straight from it = normalise, then crop, bit for bit)
         } else if (chunk_detect) {
-            if (raw) {
-                CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
-                d_img = ctx->d_image;
-            }
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, raw, false));
-            {
-                ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
-                track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
-            }
-            ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + 256 * 256 * 3));
-            crop_and_resize_launch(d_img, nb, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream);
-        } else {
-            CHK(crop_frames(ctx, src, nb, 1, H, W, bc, bs));
+            CHK(run_detect_front(ctx, src, nb, H, W, Hd, Wd, 0, MaskKeep(), &crop_src));
+            ProfScope ps(ctx, "track_select", "track_select", 0.0, 16.0 * nb);
+            track_select_launch(T.lost + b0, ctx->d_center, ctx->d_scale, nb, force_all, bc, bs, T.detected + b0, ctx->stream);
         }
-        HIPCHK(ctx, hipGetLastError());
-        CHK(run_posenet(ctx, ctx->d_crop, nb, 256, 256, true));
-        float* kpmap_out = kp_scoremap ? kp_scoremap + (size_t)b0 * 256 * 256 * 21 : nullptr;
-        int32_t* kpc_out = kp_crop ? kp_crop + (size_t)b0 * 42 : nullptr;
-        double* kpi_out = kp_image ? kp_image + (size_t)b0 * 42 : nullptr;
-        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
-            if (kpmap_out) {
-                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * nb * (32 * 32 * 21 + 256 * 256 * 21));
-                resize_bilinear_launch(ctx->d_sm[2], nb, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
-            }
-            return 0;
-        };
-        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
-            CHK(run_kp_detect(ctx, nb, kpc_out, kpi_out, dev, bs, bc));
+        CHK(crop_frames(ctx, crop_src, nb, 1, H, W, bc, bs));
+        const StepOut o = out.at(b0);
+        CHK(run_back_half(ctx, back_half_to(ctx, o, nb, fr.d_hs, bc, bs, dev, true), [&]() -> int {
             ProfScope ps(ctx, "track_box", "track_box", 0.0, 4.0 * nb * 32 * 32 * 21);
-            track_box_launch(dev && kpi_out ? kpi_out : ctx->d_kpimg, ctx->d_sm[2], 32, nb, H, W, 256, ctx->track_margin, ctx->track_min_score,
+            track_box_launch(dev && o.kp_image ? o.kp_image : ctx->d_kpimg, ctx->d_sm[2], 32, nb, H, W, 256, ctx->track_margin, ctx->track_min_score,
                              ctx->track_use_min_score, T.center[nxt] + (size_t)b0 * 2, T.scale[nxt] + b0, T.conf + b0, T.lost + b0,
                              chunk_detect ? nullptr : T.detected + b0, ctx->stream);
             return 0;
-        };
-        CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, nb, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
-        auto off = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-        CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)nb * 256 * 256 * 3, dev));
-        CHK(copy_out(ctx, off(scale_crop, 1), bs, (size_t)nb, dev));
-        CHK(copy_out(ctx, off(center, 2), bc, (size_t)nb * 2, dev));
-        if (!dev) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)nb * 256 * 256 * 21, false));
-        CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)nb * 63, dev));
-        CHK(copy_out(ctx, off(confidence, 1), T.conf + b0, (size_t)nb, dev));
-        CHK(copy_out(ctx, (float*)(lost ? lost + b0 : nullptr), (const float*)(T.lost + b0), (size_t)nb, dev));           // (int32: four bytes each, as copy_out counts)
-        CHK(copy_out(ctx, (float*)(detected ? detected + b0 : nullptr), (const float*)(T.detected + b0), (size_t)nb, dev));
+        }));
+        CHK(copy_out_slots(ctx, o, nb, bs, bc, dev));
+        CHK(copy_out(ctx, o.confidence, T.conf + b0, (size_t)nb, dev));
+        CHK(copy_out(ctx, o.lost, T.lost + b0, (size_t)nb, dev));
+        CHK(copy_out(ctx, o.detected, T.detected + b0, (size_t)nb, dev));
     }
-    HIPCHK(ctx, hipMemcpyAsync(T.h_lost, T.lost, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(T.ev_lost, ctx->stream));
-    T.pending = true;
+    CHK(T.h_lost.copy_behind(ctx, T.lost, (size_t)B));
     T.cur = nxt; T.valid = true; T.B = B; T.H = H; T.W = W; T.f = f;
     T.since = detect ? 0 : T.since + 1;
     ++(detect ? ctx->track_detect_steps : ctx->track_tracked_steps);
@@ -2136,32 +2261,12 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
 int ensure_compact(hp3d_ctx* ctx, int ns) {
     CompactBufs& Q = ctx->compact;
     if (ns <= Q.cap) return 0;
-    for (int t = 0; t < 2; ++t)
-        if (Q.busy[t]) { HIPCHK(ctx, hipEventSynchronize(Q.ev[t])); Q.busy[t] = false; }
+    for (HostFlags& h : Q.map) CHK(h.wait(ctx));
     CHK(dev_realloc(ctx, &Q.d_map, (size_t)ns * 2));
     CHK(dev_realloc(ctx, &Q.d_hs, (size_t)ns * 2));
     CHK(dev_realloc(ctx, &Q.d_center, (size_t)ns * 2));
     CHK(dev_realloc(ctx, &Q.d_scale, (size_t)ns));
-    int** hp[] = {&Q.h_map[0], &Q.h_map[1], &Q.h_valid};
-    for (int** h : hp) {
-#ifdef HP3D_EMU
-        free(*h);
-        *h = (int*)malloc(sizeof(int) * (size_t)ns * 2);
-#else
-        if (*h) HIPCHK(ctx, hipHostFree(*h));
-        *h = nullptr;
-        HIPCHK(ctx, hipHostMalloc((void**)h, sizeof(int) * (size_t)ns * 2, hipHostMallocDefault));
-#endif
-        if (!*h) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "hands_compact: host allocation failed");
-    }
-    for (int t = 0; t < 2; ++t)
-        if (!Q.ev[t]) {
-#ifdef HP3D_EMU
-            HIPCHK(ctx, hipEventCreate(&Q.ev[t]));
-#else
-            HIPCHK(ctx, hipEventCreateWithFlags(&Q.ev[t], hipEventDisableTiming));
-#endif
-        }
+    for (HostFlags* h : {&Q.map[0], &Q.map[1], &Q.valid}) CHK(h->resize(ctx, (size_t)ns * 2, "hands_compact"));
     Q.cap = ns;
     return 0;
 }
@@ -2170,15 +2275,7 @@ void compact_free(hp3d_ctx* ctx) {
     CompactBufs& Q = ctx->compact;
     for (void* p : {(void*)Q.d_map, (void*)Q.d_hs, (void*)Q.d_center, (void*)Q.d_scale})
         if (p) hipFree(p);
-    for (int* h : {Q.h_map[0], Q.h_map[1], Q.h_valid}) {
-#ifdef HP3D_EMU
-        free(h);
-#else
-        if (h) hipHostFree(h);
-#endif
-    }
-    for (int t = 0; t < 2; ++t)
-        if (Q.ev[t]) hipEventDestroy(Q.ev[t]);
+    for (HostFlags* h : {&Q.map[0], &Q.map[1], &Q.valid}) h->free();
     Q = CompactBufs();
 }
 
@@ -2187,10 +2284,10 @@ void compact_free(hp3d_ctx* ctx) {
 // state's flags are on the host already.
 int compact_wait_flags(hp3d_ctx* ctx, const int* d_valid, int ns, const int** h_valid) {
     CHK(ensure_compact(ctx, ns));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->compact.h_valid, d_valid, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->compact.valid.h, d_valid, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ++ctx->hands_compact_waits;
-    *h_valid = ctx->compact.h_valid;
+    *h_valid = ctx->compact.valid.h;
     return 0;
 }
 
@@ -2198,18 +2295,13 @@ int compact_wait_flags(hp3d_ctx* ctx, const int* d_valid, int ns, const int** h_
 struct CompactChunk {
     int nb, K, H, W;
     const int* h_valid;                  // host: the chunk's nb * K flags
-    const float* d_img;                  // the chunk's frames, float32 ...
-    const unsigned char* d_u8;           // ... or, when not null, uint8: the crop comes straight from them
+    FrameSrc src;                        // what the crops are taken from
     const float *center, *scale, *hand_side;      // device, slot layout
-    float *image_crop, *kp_scoremap, *coord3d;    // the chunk's outputs, slot layout (null: skipped); device pointers when dev
-    int32_t* kp_crop;
-    double* kp_image;
+    StepOut out;                         // the chunk's outputs, slot layout: image_crop, kp_scoremap, coord3d, kp_crop and kp_image are written here
     bool dev;
     bool want_kp;                        // run kp_detect (hp3d_infer_hands*: only when asked for; the tracker: always)
     // the multi-hand tracker's box step (null: hp3d_infer_hands*): the chunk's slice of the state
     const std::function<void(const double* kp_image_dense, const int* pos)>* box = nullptr;
-    const Nv12Src* nv12 = nullptr;       // ... or NV12: d_img and d_u8 are then unused
-    FrameSrc src() const { FrameSrc f; f.f32 = d_img; f.u8 = d_u8; f.nv12 = nv12; return f; }
 };
 
 // The back half at batch m = the chunk's valid slots.  *compacted = false (m = ns: no absent slot): nothing is enqueued, the caller
@@ -2227,13 +2319,13 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
     if (m == ns) return 0;
     CHK(ensure_compact(ctx, ns));
     CompactBufs& Q = ctx->compact;
-    const int t = Q.turn;
+    HostFlags& map = Q.map[Q.turn];
     Q.turn ^= 1;
     // (an event wait on the upload of two compacted chunks ago, not a stream synchronise and not counted: it can hold the host only in
     //  a call of three or more compacted chunks that runs ahead of the device by two of them; ensure_compact waits likewise when the
     //  slot count grows)
-    if (Q.busy[t]) { HIPCHK(ctx, hipEventSynchronize(Q.ev[t])); Q.busy[t] = false; }
-    int* idx = Q.h_map[t];
+    CHK(map.wait(ctx));
+    int* idx = map.h;
     int* pos = idx + ns;
     for (int s = 0, i = 0; s < ns; ++s) {
         pos[s] = c.h_valid[s] ? i : -1;
@@ -2241,8 +2333,7 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
     }
     for (int i = m; i < ns; ++i) idx[i] = 0;
     HIPCHK(ctx, hipMemcpyAsync(Q.d_map, idx, sizeof(int) * (size_t)ns * 2, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(Q.ev[t], ctx->stream));
-    Q.busy[t] = true;
+    CHK(map.record(ctx));
     const int* d_idx = Q.d_map;
     const int* d_pos = Q.d_map + ns;
     if (m > 0) {
@@ -2250,21 +2341,13 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
             ProfScope ps(ctx, "slot_gather", "slot_gather", 0.0, 24.0 * m);
             slot_gather_launch(d_idx, m, c.hand_side, c.center, c.scale, Q.d_hs, Q.d_center, Q.d_scale, ctx->stream);
         }
-        CHK(crop_frames_idx(ctx, c.src(), c.nb, c.K, c.H, c.W, c.center, c.scale, d_idx, m));
-        CHK(run_posenet(ctx, ctx->d_crop, m, 256, 256, true));
-        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
-            if (c.kp_scoremap) {
-                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * m * (32 * 32 * 21 + 256 * 256 * 21));
-                resize_bilinear_launch(ctx->d_sm[2], m, 32, 32, 21, 32, 256, 256, ctx->d_kpmap, st);
-            }
-            return 0;
-        };
-        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
-            if (c.want_kp) CHK(run_kp_detect(ctx, m, nullptr, nullptr, true, Q.d_scale, Q.d_center));
+        CHK(crop_frames_idx(ctx, c.src, c.nb, c.K, c.H, c.W, c.center, c.scale, d_idx, m));
+        // (the dense maps and keypoints stay in d_kpmap / d_kpcrop / d_kpimg: the scatter below takes them to the caller)
+        const BackHalf b{m, Q.d_hs, Q.d_center, Q.d_scale, c.out.kp_scoremap ? ctx->d_kpmap : nullptr, nullptr, nullptr, true, c.want_kp};
+        CHK(run_back_half(ctx, b, [&]() -> int {
             if (c.box) (*c.box)(ctx->d_kpimg, d_pos);
             return 0;
-        };
-        CHK(run_pose3d(ctx, ctx->d_sm[2], Q.d_hs, m, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+        }));
     } else if (c.box) {
         (*c.box)(ctx->d_kpimg, d_pos);
     }
@@ -2276,31 +2359,26 @@ int run_compact_back_half(hp3d_ctx* ctx, const CompactChunk& c, bool* compacted)
     float* s_coord = stage((size_t)ns * 63);
     float* s_kpcrop = stage((size_t)ns * 42);
     float* s_kpimg = stage((size_t)ns * 84);
+    const StepOut& o = c.out;
     ScatterPlan plan;
-    plan.add(ctx->d_crop, c.image_crop ? (c.dev ? c.image_crop : s_crop) : nullptr, 256 * 256 * 3);
-    plan.add(ctx->d_kpmap, c.kp_scoremap ? (c.dev ? c.kp_scoremap : s_kpmap) : nullptr, 256 * 256 * 21);
-    plan.add(ctx->d_coord, c.coord3d ? (c.dev ? c.coord3d : s_coord) : nullptr, 63);
-    plan.add(ctx->d_kpcrop, c.kp_crop ? (c.dev ? (float*)c.kp_crop : s_kpcrop) : nullptr, 42);
-    plan.add(ctx->d_kpimg, c.kp_image ? (c.dev ? (float*)c.kp_image : s_kpimg) : nullptr, 84);
+    plan.add(ctx->d_crop, o.image_crop ? (c.dev ? o.image_crop : s_crop) : nullptr, 256 * 256 * 3);
+    plan.add(ctx->d_kpmap, o.kp_scoremap ? (c.dev ? o.kp_scoremap : s_kpmap) : nullptr, 256 * 256 * 21);
+    plan.add(ctx->d_coord, o.coord3d ? (c.dev ? o.coord3d : s_coord) : nullptr, 63);
+    plan.add(ctx->d_kpcrop, o.kp_crop ? (c.dev ? (float*)o.kp_crop : s_kpcrop) : nullptr, 42);
+    plan.add(ctx->d_kpimg, o.kp_image ? (c.dev ? (float*)o.kp_image : s_kpimg) : nullptr, 84);
     if (plan.n > 0) {
         ProfScope ps(ctx, "slot_scatter", "slot_scatter", 0.0, plan.bytes(ns, m));
         slot_scatter_launch(plan, d_pos, ns, ctx->stream);
     }
     HIPCHK(ctx, hipGetLastError());
     if (!c.dev) {
-        CHK(copy_out(ctx, c.image_crop, s_crop, (size_t)ns * 256 * 256 * 3, false));
-        CHK(copy_out(ctx, c.kp_scoremap, s_kpmap, (size_t)ns * 256 * 256 * 21, false));
-        CHK(copy_out(ctx, c.coord3d, s_coord, (size_t)ns * 63, false));
-        CHK(copy_out(ctx, (float*)c.kp_crop, s_kpcrop, (size_t)ns * 42, false));           // (int32 / float64: four bytes a word, as copy_out counts)
-        CHK(copy_out(ctx, (float*)c.kp_image, s_kpimg, (size_t)ns * 84, false));
+        CHK(copy_out(ctx, o.image_crop, s_crop, (size_t)ns * 256 * 256 * 3, false));
+        CHK(copy_out(ctx, o.kp_scoremap, s_kpmap, (size_t)ns * 256 * 256 * 21, false));
+        CHK(copy_out(ctx, o.coord3d, s_coord, (size_t)ns * 63, false));
+        CHK(copy_out(ctx, (float*)o.kp_crop, s_kpcrop, (size_t)ns * 42, false));           // (int32 / float64: four bytes a word, as copy_out counts)
+        CHK(copy_out(ctx, (float*)o.kp_image, s_kpimg, (size_t)ns * 84, false));
     }
     return 0;
-}
-
-// The crop of every slot of a chunk, for a compacted call's chunk without an absent slot: the launch and the profile row of the
-// uncompacted path.
-int crop_all_slots(hp3d_ctx* ctx, const CompactChunk& c) {
-    return crop_frames(ctx, c.src(), c.nb, c.K, c.H, c.W, c.center, c.scale);
 }
 
 // Up to K hands per frame: HandSegNet, the soft-max and ONE multi-hand mask growth per chunk of frames, then the back
@@ -2308,33 +2386,31 @@ int crop_all_slots(hp3d_ctx* ctx, const CompactChunk& c) {
 // batch nb * K with per-slot centre / scale / hand_side.  No compaction unless option "hands_compact" (DESIGN.md 4.15): absent slots run on their fall-back crop, so a call has one
 // kernel plan and no host wait.  A chunk holds at most micro_batch / K frames: no launch behind the crop sees more slots than a
 // single-hand call's chunk has images.  One stream, no graph replay.
-int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, int Hin, int Win,
-                     const float* hand_side, float* hand_scoremap, float* image_crop, float* scale_crop, float* center, float* kp_scoremap,
-                     float* coord3d, float* hand_mask, int32_t* kp_crop, double* kp_image, int32_t* valid, int32_t* area, bool dev) {
+// (in.image_u8: host frames of Hin x Win, resized to the network's size; out.valid / out.area: per slot)
+int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepIn& in, int Hin, int Win, const StepOut& out, float* hand_scoremap,
+                     float* hand_mask) {
     if (!ctx) return HP3D_ERR_ARG;
-    if ((!image && !image_u8) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+    const unsigned char* image_u8 = in.image_u8;
+    const bool dev = in.dev;
+    if ((!in.image && !image_u8) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
     if (image_u8 && (Hin < 2 || Win < 2)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad uint8 frame size %dx%d", Hin, Win);
     CHK(check_img(ctx, B, H, W));
     CHK(need_nets(ctx, NET_SEG | NET_POSE | NET_PRIOR | NET_VP));
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int front = auto_micro_batch(ctx, B, H, W), back = auto_micro_batch(ctx, B * K, 256, 256);
-    int mb = front <= 0 ? B : std::min(front, B);
-    if (back > 0) mb = std::min(mb, std::max(1, back / K));
+    const int mb = slot_micro_batch(ctx, B, K, H, W);
     CHK(ensure_arena(ctx, mb, H, W, mb * K));
     if (hand_mask && (size_t)mb * K * H * W > ctx->mask_floats) {
         CHK(dev_realloc(ctx, &ctx->d_mask, (size_t)mb * K * H * W));
         ctx->mask_floats = (size_t)mb * K * H * W;
     }
-    const int saved_prof = ctx->profiling;
-    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
-    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    ProfCall prof(ctx);
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = std::min(mb, B - b0), ns = nb * K;
         const size_t s0 = (size_t)b0 * K;
-        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one call = one profile: keep the earlier chunks
-        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
-        const float* d_hs = hand_side + s0 * 2;
+        prof.chunk(b0);
+        const float* d_img = in.image ? in.image + (size_t)b0 * H * W * 3 : nullptr;
+        const float* d_hs = in.hand_side + s0 * 2;
         if (image_u8) {
             const size_t nbytes = (size_t)nb * Hin * Win * 3;
             if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
@@ -2346,43 +2422,26 @@ int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
             d_img = ctx->d_image;
         }
         if (!dev) { CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false)); d_hs = ctx->d_hs; }
-        float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
-        int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
-        double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
-        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        const StepOut o = out.at(s0);
+        const bool want_kp = o.kp_crop || o.kp_image;
+        FrameSrc src;
+        src.f32 = d_img;
+        CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, false, K));
         bool compacted = false;          // option "hands_compact": the back half ran on the valid slots only and wrote its outputs
         if (ctx->hands_compact) {
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, false, K));
-            CompactChunk cc{nb, K, H, W, nullptr, d_img, nullptr, ctx->d_center, ctx->d_scale, d_hs, off(image_crop, 256 * 256 * 3), kpmap_out,
-                            off(coord3d, 63), kpc_out, kpi_out, dev, kpc_out || kpi_out};
+            CompactChunk cc{nb, K, H, W, nullptr, src, ctx->d_center, ctx->d_scale, d_hs, o, dev, want_kp};
             CHK(compact_wait_flags(ctx, ctx->d_valid, ns, &cc.h_valid));
             CHK(run_compact_back_half(ctx, cc, &compacted));
-            if (!compacted) CHK(crop_all_slots(ctx, cc));
-        } else {
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, hand_mask != nullptr, image_u8 != nullptr, true, K));
         }
-        if (!compacted) CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
-        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
-            if (kpmap_out) {
-                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
-                resize_bilinear_launch(ctx->d_sm[2], ns, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
-            }
-            return 0;
-        };
-        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
-            if (kpc_out || kpi_out) CHK(run_kp_detect(ctx, ns, kpc_out, kpi_out, dev));
-            return 0;
-        };
-        if (!compacted) CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
+        if (!compacted) {
+            CHK(crop_frames(ctx, src, nb, K, H, W, ctx->d_center, ctx->d_scale));
+            CHK(run_back_half(ctx, back_half_to(ctx, o, ns, d_hs, nullptr, nullptr, dev, want_kp), [] { return 0; }));
+        }
         CHK(copy_out(ctx, hand_scoremap ? hand_scoremap + (size_t)b0 * H * W * 2 : nullptr, ctx->d_large, (size_t)nb * H * W * 2, dev));
-        if (!compacted) CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
-        CHK(copy_out(ctx, off(scale_crop, 1), ctx->d_scale, (size_t)ns, dev));
-        CHK(copy_out(ctx, off(center, 2), ctx->d_center, (size_t)ns * 2, dev));
-        if (!dev && !compacted) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
-        if (!compacted) CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
-        CHK(copy_out(ctx, off(hand_mask, (size_t)H * W), ctx->d_mask, (size_t)ns * H * W, dev));
-        CHK(copy_out(ctx, (float*)(valid ? valid + s0 : nullptr), (const float*)ctx->d_valid, (size_t)ns, dev));           // (int32: four bytes each, as copy_out counts)
-        CHK(copy_out(ctx, (float*)(area ? area + s0 : nullptr), (const float*)ctx->d_area, (size_t)ns, dev));
+        CHK(copy_out_slots(ctx, o, ns, ctx->d_scale, ctx->d_center, dev, !compacted));
+        CHK(copy_out(ctx, hand_mask ? hand_mask + s0 * H * W : nullptr, ctx->d_mask, (size_t)ns * H * W, dev));
+        CHK(copy_out(ctx, o.valid, ctx->d_valid, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.area, ctx->d_area, (size_t)ns, dev));
     }
     if (!dev) return finish_op(ctx);
     return 0;
@@ -2392,7 +2451,7 @@ int infer_hands_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
 int ensure_track_hands(hp3d_ctx* ctx, int n) {
     TrackHandsState& T = ctx->track_hands;
     if (n <= T.cap) return 0;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }
+    CHK(T.h_flags.wait(ctx));
     for (int i = 0; i < 2; ++i) {
         CHK(dev_realloc(ctx, &T.center[i], (size_t)n * 2));
         CHK(dev_realloc(ctx, &T.scale[i], (size_t)n));
@@ -2403,17 +2462,7 @@ int ensure_track_hands(hp3d_ctx* ctx, int n) {
     CHK(dev_realloc(ctx, &T.area, (size_t)n));
     CHK(dev_realloc(ctx, &T.claimed, (size_t)n));
     CHK(dev_realloc(ctx, &T.keep, (size_t)n));
-#ifdef HP3D_EMU
-    free(T.h_flags);
-    T.h_flags = (int*)malloc(sizeof(int) * (size_t)n * 2);
-    if (!T.ev_flags) HIPCHK(ctx, hipEventCreate(&T.ev_flags));
-#else
-    if (T.h_flags) HIPCHK(ctx, hipHostFree(T.h_flags));
-    T.h_flags = nullptr;
-    HIPCHK(ctx, hipHostMalloc((void**)&T.h_flags, sizeof(int) * (size_t)n * 2, hipHostMallocDefault));
-    if (!T.ev_flags) HIPCHK(ctx, hipEventCreateWithFlags(&T.ev_flags, hipEventDisableTiming));
-#endif
-    if (!T.h_flags) HP3D_FAIL(ctx, HP3D_ERR_NOMEM, "multi-hand tracking state: host allocation failed");
+    CHK(T.h_flags.resize(ctx, (size_t)n * 2, "multi-hand tracking state"));
     T.cap = n;
     T.ok = false;
     return 0;
@@ -2427,12 +2476,7 @@ void track_hands_free(hp3d_ctx* ctx) {
     }
     for (void* p : {(void*)T.conf, (void*)T.flags, (void*)T.detected, (void*)T.area, (void*)T.claimed, (void*)T.keep})
         if (p) hipFree(p);
-#ifdef HP3D_EMU
-    free(T.h_flags);
-#else
-    if (T.h_flags) hipHostFree(T.h_flags);
-#endif
-    if (T.ev_flags) hipEventDestroy(T.ev_flags);
+    T.h_flags.free();
     T = TrackHandsState();
 }
 
@@ -2443,23 +2487,18 @@ void track_hands_free(hp3d_ctx* ctx) {
 // at batch nb * K plus the per-slot box rule.  Decided on the host, before anything is enqueued, from the valid | lost flags that travel
 // behind the previous step; the whole batch detects together; absent slots run on their fall-back crop (no compaction unless option
 // "hands_compact", DESIGN.md 4.15: run_compact_back_half).
-// (The frame of this function -- uint8 upload, profile save / restore, chunk loop, kp_up / kp_work, copy_out sequence -- repeats
-//  track_step_impl's, which this change leaves as it is: a fix to one of the two belongs in the other as well.)
-int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const unsigned char* image_u8, const float* hand_side,
-                          float* image_crop, float* scale_crop, float* center, float* kp_scoremap, float* coord3d, int32_t* kp_crop,
-                          double* kp_image, float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area,
-                          int32_t* claimed, bool dev, const Nv12Arg* nv = nullptr) {
-    if ((!image && !image_u8 && !nv) || !hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
+int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepIn& in, const StepOut& out) {
+    if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
-    if (nv) CHK(check_nv12(ctx, B, H, W, *nv));
+    if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
     CHK(check_img(ctx, B, H, W));
-    const bool raw = image_u8 || nv;                     // uint8 or NV12 frames: no float32 frame comes in
+    const bool dev = in.dev;
     int Hd, Wd;
     CHK(detect_frame(ctx, H, W, &Hd, &Wd));
     const int f = ctx->detect_scale;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TrackHandsState& T = ctx->track_hands;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }     // the only wait tracking adds: the previous step's flags
+    CHK(T.h_flags.wait(ctx));                            // the only wait tracking adds: the previous step's flags
     const int n = B * K;
     const bool fresh = !T.ok || T.B != B || T.K != K || T.H != H || T.W != W || T.f != f;
     bool any_lost = false, no_hand = false;      // a valid slot was lost / an image has nothing to follow
@@ -2467,146 +2506,80 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const float
         for (int b = 0; b < B; ++b) {
             bool any_valid = false;
             for (int j = 0; j < K; ++j) {
-                const bool v = T.h_flags[b * K + j] != 0;
+                const bool v = T.h_flags.h[b * K + j] != 0;
                 any_valid = any_valid || v;
-                any_lost = any_lost || (v && T.h_flags[n + b * K + j] != 0);
+                any_lost = any_lost || (v && T.h_flags.h[n + b * K + j] != 0);
             }
             no_hand = no_hand || !any_valid;
         }
     const bool sched = ctx->track_redetect > 0 && T.since + 1 >= ctx->track_redetect;
     const bool detect = fresh || any_lost || no_hand || sched;
     CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
-    const int front = auto_micro_batch(ctx, B, Hd, Wd), back = auto_micro_batch(ctx, n, 256, 256);
-    int mb = front <= 0 ? B : std::min(front, B);
-    if (back > 0) mb = std::min(mb, std::max(1, back / K));
+    const int mb = slot_micro_batch(ctx, B, K, Hd, Wd);
     CHK(ensure_arena(ctx, mb, Hd, Wd, mb * K));
-    if (f > 1 && !dev && !raw) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    if (f > 1 && !dev && !in.raw()) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track_hands(ctx, n));
     T.ok = false;                                        // a step that fails half way leaves no state behind
     T.B = B; T.K = K; T.H = H; T.W = W; T.f = f;         // (the flags' layout: lost() = flags + B K)
     if (fresh) HIPCHK(ctx, hipMemsetAsync(T.keep, 0, sizeof(int) * (size_t)n, ctx->stream));      // nothing to keep
-    if (image_u8) {
-        const size_t nbytes = (size_t)B * H * W * 3;
-        if (nbytes > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, nbytes)); ctx->u8_bytes = nbytes; }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, image_u8, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    Nv12Src nvs{};                                       // NV12 frames: the caller's surfaces in place (dev) or their packed upload
-    if (nv && dev) nvs = nv12_src(nv->y, nv->uv, nv->pitch, B > 1 ? (size_t)nv->frame_stride : 0, ctx->nv12_matrix);
-    else if (nv) CHK(upload_nv12(ctx, B, H, W, *nv, &nvs));
-    const int saved_prof = ctx->profiling;
-    struct ProfRestore { hp3d_ctx* c; int v; ~ProfRestore() { c->profiling = v; } } prof_restore{ctx, saved_prof};   // every exit path
-    if (ctx->profiling != 2) prof_reset(ctx);   // mode 2 accumulates across calls
+    StepFrames fr{in, H, W};
+    CHK(fr.upload(ctx, B));
+    ProfCall prof(ctx);
     const int cur = T.cur, nxt = T.cur ^ 1;
-    const bool comp = ctx->hands_compact != 0;
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = std::min(mb, B - b0), ns = nb * K;
         const size_t s0 = (size_t)b0 * K;
-        if (b0 > 0 && saved_prof == 1) ctx->profiling = 2;          // one step = one profile: keep the earlier chunks
-        const float* d_img = image ? image + (size_t)b0 * H * W * 3 : nullptr;
-        const float* d_hs = hand_side + s0 * 2;
-        const unsigned char* d_u8 = image_u8 ? ctx->d_u8 + (size_t)b0 * H * W * 3 : nullptr;
-        if (!dev) {
-            CHK(copy_in(ctx, ctx->d_hs, d_hs, (size_t)ns * 2, false));
-            d_hs = ctx->d_hs;
-            if (!raw) {
-                float* stage = f > 1 ? ctx->d_stage : ctx->d_image;
-                CHK(copy_in(ctx, stage, d_img, (size_t)nb * H * W * 3, false));
-                d_img = stage;
-            }
-        }
-        const Nv12Src nvc = nvs.at(b0);
-        FrameSrc src;
-        src.f32 = d_img; src.u8 = d_u8; src.nv12 = nv ? &nvc : nullptr;
+        prof.chunk(b0);
+        CHK(fr.chunk(ctx, b0, nb, K, f > 1));
+        FrameSrc crop_src = fr.src;
         float* bc = T.center[cur] + s0 * 2;
         float* bs = T.scale[cur] + s0;
-        if (detect && f > 1) {
+        if (detect) {
             MaskKeep mk;
             mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
-            CHK(run_detect_reduced(ctx, src, nb, H, W, Hd, Wd, K, mk));
-            {
-                ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
-                track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
-                                          T.detected + s0, T.area + s0, ctx->stream);
-            }
-            if (!comp) CHK(crop_frames(ctx, src, nb, K, H, W, bc, bs));          // (comp: the crop follows the flags, below)
-        } else if (detect) {
-            if (raw) {
-                CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
-                d_img = ctx->d_image;
-            }
-            MaskKeep mk;
-            mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
-            CHK(run_detect_and_crop(ctx, d_img, nb, H, W, 0, raw, false, K, mk));
-            {
-                ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
-                track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
-                                          T.detected + s0, T.area + s0, ctx->stream);
-            }
-            if (!comp) {
-                ProfScope ps(ctx, "crop_and_resize", "crop_and_resize", 0.0, 4.0 * nb * (H * W * 3 + K * 256 * 256 * 3));
-                crop_and_resize_launch(d_img, ns, H, W, 3, bc, bs, 256, ctx->d_crop, ctx->stream, K);
-            }
-        } else if (!comp) {          // (comp, a tracked step: the state's flags are on the host already)
-            CHK(crop_frames(ctx, src, nb, K, H, W, bc, bs));
+            CHK(run_detect_front(ctx, fr.src, nb, H, W, Hd, Wd, K, mk, &crop_src));
+            ProfScope ps(ctx, "track_hands_select", "track_hands_select", 0.0, 40.0 * ns);
+            track_hands_select_launch(T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, ns, bc, bs, T.valid() + s0,
+                                      T.detected + s0, T.area + s0, ctx->stream);
         }
         HIPCHK(ctx, hipGetLastError());
-        float* kpmap_out = kp_scoremap ? kp_scoremap + s0 * 256 * 256 * 21 : nullptr;
-        int32_t* kpc_out = kp_crop ? kp_crop + s0 * 42 : nullptr;
-        double* kpi_out = kp_image ? kp_image + s0 * 42 : nullptr;
-        auto off = [&](float* p, size_t per) { return p ? p + s0 * per : nullptr; };
+        const StepOut o = out.at(s0);
+        // the state a tracked step's box rule also clears (a detect step's select has written it)
+        int* detected0 = detect ? nullptr : T.detected + s0;
+        int* area0 = detect ? nullptr : T.area + s0;
+        int* claimed0 = detect ? nullptr : T.claimed + s0;
         bool compacted = false;          // option "hands_compact": the back half ran on the valid slots only and wrote its outputs
-        if (comp) {
-            // (a detect step at detect_scale = 1 has normalised a uint8 frame for HandSegNet and crops from that, as without the option)
+        if (ctx->hands_compact) {
             const std::function<void(const double*, const int*)> box = [&](const double* kp_dense, const int* d_pos) {
                 ProfScope ps(ctx, "track_hands_box", "track_hands_box_pos", 0.0, 4.0 * ns * 32 * 32 * 21);
                 track_hands_box_pos_launch(kp_dense, ctx->d_sm[2], 32, ns, H, W, 256, ctx->track_margin, ctx->track_min_score,
                                            ctx->track_use_min_score, d_pos, bc, bs, T.center[nxt] + s0 * 2, T.scale[nxt] + s0, T.conf + s0,
-                                           T.lost() + s0, T.keep + s0, detect ? nullptr : T.detected + s0, detect ? nullptr : T.area + s0,
-                                           detect ? nullptr : T.claimed + s0, ctx->stream);
+                                           T.lost() + s0, T.keep + s0, detected0, area0, claimed0, ctx->stream);
             };
-            CompactChunk cc{nb, K, H, W, T.h_flags + s0, d_img, image_u8 && (!detect || f > 1) ? d_u8 : nullptr, bc, bs, d_hs,
-                            off(image_crop, 256 * 256 * 3), kpmap_out, off(coord3d, 63), kpc_out, kpi_out, dev, true, &box};
-            // (likewise an NV12 frame; where the crop comes from the frame, d_img is not read)
-            cc.nv12 = (nv && (!detect || f > 1)) ? &nvc : nullptr;
+            // (a tracked step: the state's flags are on the host already)
+            CompactChunk cc{nb, K, H, W, T.h_flags.h + s0, crop_src, bc, bs, fr.d_hs, o, dev, true, &box};
             if (detect) CHK(compact_wait_flags(ctx, T.valid() + s0, ns, &cc.h_valid));
             CHK(run_compact_back_half(ctx, cc, &compacted));
-            if (!compacted) CHK(crop_all_slots(ctx, cc));
         }
-        if (!compacted) CHK(run_posenet(ctx, ctx->d_crop, ns, 256, 256, true));
-        const std::function<int(hipStream_t)> kp_up = [&](hipStream_t st) -> int {
-            if (kpmap_out) {
-                ProfScope ps(ctx, "kp_upsample", "resize_bilinear", 0.0, 4.0 * ns * (32 * 32 * 21 + 256 * 256 * 21));
-                resize_bilinear_launch(ctx->d_sm[2], ns, 32, 32, 21, 32, 256, 256, dev ? kpmap_out : ctx->d_kpmap, st);
-            }
-            return 0;
-        };
-        const std::function<int(hipStream_t)> kp_work = [&](hipStream_t) -> int {
-            CHK(run_kp_detect(ctx, ns, kpc_out, kpi_out, dev, bs, bc));
-            ProfScope ps(ctx, "track_hands_box", "track_hands_box", 0.0, 4.0 * ns * 32 * 32 * 21);
-            int* zero = detect ? nullptr : T.detected + s0;
-            track_hands_box_launch(dev && kpi_out ? kpi_out : ctx->d_kpimg, ctx->d_sm[2], 32, ns, H, W, 256, ctx->track_margin,
-                                   ctx->track_min_score, ctx->track_use_min_score, T.valid() + s0, bc, bs, T.center[nxt] + s0 * 2,
-                                   T.scale[nxt] + s0, T.conf + s0, T.lost() + s0, T.keep + s0, zero, detect ? nullptr : T.area + s0,
-                                   detect ? nullptr : T.claimed + s0, ctx->stream);
-            return 0;
-        };
-        if (!compacted) CHK(run_pose3d(ctx, ctx->d_sm[2], d_hs, ns, HP3D_VARIANT_PROPOSED, &kp_work, &kp_up));
-        auto offi = [&](int32_t* p) { return (float*)(p ? p + s0 : nullptr); };           // (int32: four bytes each, as copy_out counts)
-        if (!compacted) CHK(copy_out(ctx, off(image_crop, 256 * 256 * 3), ctx->d_crop, (size_t)ns * 256 * 256 * 3, dev));
-        CHK(copy_out(ctx, off(scale_crop, 1), bs, (size_t)ns, dev));
-        CHK(copy_out(ctx, off(center, 2), bc, (size_t)ns * 2, dev));
-        if (!dev && !compacted) CHK(copy_out(ctx, kpmap_out, ctx->d_kpmap, (size_t)ns * 256 * 256 * 21, false));
-        if (!compacted) CHK(copy_out(ctx, off(coord3d, 63), ctx->d_coord, (size_t)ns * 63, dev));
-        CHK(copy_out(ctx, off(confidence, 1), T.conf + s0, (size_t)ns, dev));
-        CHK(copy_out(ctx, offi(lost), (const float*)(T.lost() + s0), (size_t)ns, dev));
-        CHK(copy_out(ctx, offi(detected), (const float*)(T.detected + s0), (size_t)ns, dev));
-        CHK(copy_out(ctx, offi(valid), (const float*)(T.valid() + s0), (size_t)ns, dev));
-        CHK(copy_out(ctx, offi(area), (const float*)(T.area + s0), (size_t)ns, dev));
-        CHK(copy_out(ctx, offi(claimed), (const float*)(T.claimed + s0), (size_t)ns, dev));
+        if (!compacted) {
+            CHK(crop_frames(ctx, crop_src, nb, K, H, W, bc, bs));
+            CHK(run_back_half(ctx, back_half_to(ctx, o, ns, fr.d_hs, bc, bs, dev, true), [&]() -> int {
+                ProfScope ps(ctx, "track_hands_box", "track_hands_box", 0.0, 4.0 * ns * 32 * 32 * 21);
+                track_hands_box_launch(dev && o.kp_image ? o.kp_image : ctx->d_kpimg, ctx->d_sm[2], 32, ns, H, W, 256, ctx->track_margin,
+                                       ctx->track_min_score, ctx->track_use_min_score, T.valid() + s0, bc, bs, T.center[nxt] + s0 * 2,
+                                       T.scale[nxt] + s0, T.conf + s0, T.lost() + s0, T.keep + s0, detected0, area0, claimed0, ctx->stream);
+                return 0;
+            }));
+        }
+        CHK(copy_out_slots(ctx, o, ns, bs, bc, dev, !compacted));
+        CHK(copy_out(ctx, o.confidence, T.conf + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.lost, T.lost() + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.detected, T.detected + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.valid, T.valid() + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.area, T.area + s0, (size_t)ns, dev));
+        CHK(copy_out(ctx, o.claimed, T.claimed + s0, (size_t)ns, dev));
     }
-    HIPCHK(ctx, hipMemcpyAsync(T.h_flags, T.flags, sizeof(int) * (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(T.ev_flags, ctx->stream));
-    T.pending = true;
+    CHK(T.h_flags.copy_behind(ctx, T.flags, (size_t)n * 2));
     T.cur = nxt; T.ok = true;
     T.since = detect ? 0 : T.since + 1;
     ++(detect ? ctx->track_hands_detect_steps : ctx->track_hands_tracked_steps);
@@ -3219,16 +3192,18 @@ int hp3d_infer_hands(hp3d_ctx* ctx, int B, int H, int W, int K, const float* ima
                      float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return infer_hands_impl(ctx, B, H, W, K, image, nullptr, 0, 0, hand_side, hand_scoremap, image_crop, scale_crop, center,
-                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, false);
+    return infer_hands_impl(ctx, B, H, W, K, StepIn{image, nullptr, nullptr, hand_side, false}, 0, 0,
+                            StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                    nullptr, nullptr, nullptr, valid, area}, hand_scoremap, hand_mask);
 }
 int hp3d_infer_hands_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* hand_scoremap,
                          float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
                          float* hand_mask, int32_t* keypoint_hw_crop, double* keypoint_hw, int32_t* valid, int32_t* area) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return infer_hands_impl(ctx, B, H, W, K, image, nullptr, 0, 0, hand_side, hand_scoremap, image_crop, scale_crop, center,
-                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, true);
+    return infer_hands_impl(ctx, B, H, W, K, StepIn{image, nullptr, nullptr, hand_side, true}, 0, 0,
+                            StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                    nullptr, nullptr, nullptr, valid, area}, hand_scoremap, hand_mask);
 }
 int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
                         float* hand_scoremap, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
@@ -3236,8 +3211,9 @@ int hp3d_infer_hands_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* i
                         int32_t* area) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return infer_hands_impl(ctx, B, H, W, K, nullptr, image_u8, Hin, Win, hand_side, hand_scoremap, image_crop, scale_crop, center,
-                            keypoints_scoremap, keypoint_coord3d, hand_mask, keypoint_hw_crop, keypoint_hw, valid, area, false);
+    return infer_hands_impl(ctx, B, H, W, K, StepIn{nullptr, image_u8, nullptr, hand_side, false}, Hin, Win,
+                            StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                    nullptr, nullptr, nullptr, valid, area}, hand_scoremap, hand_mask);
 }
 
 static int masks_from_scoremap_impl(hp3d_ctx* ctx, const float* scoremap, int B, int H, int W, int K, const int32_t* keep,
@@ -3341,7 +3317,7 @@ int hp3d_track_hands_seed(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(ensure_track_hands(ctx, n));
     TrackHandsState& T = ctx->track_hands;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_flags)); T.pending = false; }
+    CHK(T.h_flags.wait(ctx));
     T.ok = false;
     T.B = B; T.K = K; T.H = H; T.W = W; T.f = ctx->detect_scale;
     HIPCHK(ctx, hipMemcpyAsync(T.center[T.cur], c.data(), sizeof(float) * (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -3350,7 +3326,7 @@ int hp3d_track_hands_seed(hp3d_ctx* ctx, int B, int H, int W, int K, const float
     HIPCHK(ctx, hipMemcpyAsync(T.keep, v.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(T.lost(), 0, sizeof(int) * (size_t)n, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < n; ++i) { T.h_flags[i] = v[i]; T.h_flags[n + i] = 0; }
+    for (int i = 0; i < n; ++i) { T.h_flags.h[i] = v[i]; T.h_flags.h[n + i] = 0; }
     T.ok = true; T.since = 0;
     return 0;
 }
@@ -3361,8 +3337,9 @@ int hp3d_track_hands_step(hp3d_ctx* ctx, int B, int H, int W, int K, const float
                           int32_t* claimed) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return track_hands_step_impl(ctx, B, H, W, K, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false);
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{image, nullptr, nullptr, hand_side, false},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 int hp3d_track_hands_step_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const float* image, const float* hand_side, float* image_crop,
                               float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
@@ -3370,8 +3347,9 @@ int hp3d_track_hands_step_dev(hp3d_ctx* ctx, int B, int H, int W, int K, const f
                               int32_t* valid, int32_t* area, int32_t* claimed) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return track_hands_step_impl(ctx, B, H, W, K, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, true);
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{image, nullptr, nullptr, hand_side, true},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, int K, const float* hand_side,
                              float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
@@ -3381,8 +3359,9 @@ int hp3d_track_hands_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8
     if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (Hin != H || Win != W)
         HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "tracking crops straight from the uint8 frame: the frame (%dx%d) must have the network size (%dx%d)", Hin, Win, H, W);
-    return track_hands_step_impl(ctx, B, H, W, K, nullptr, image_u8, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false);
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, image_u8, nullptr, hand_side, false},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 
 int hp3d_track_hands_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride, int K,
@@ -3391,8 +3370,9 @@ int hp3d_track_hands_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t
                                int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
     if (!ctx) return HP3D_ERR_ARG;
     const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
-    return track_hands_step_impl(ctx, B, H, W, K, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, false, &nv);
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, &nv, hand_side, false},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 int hp3d_track_hands_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
                                    int K, const float* hand_side, float* image_crop, float* scale_crop, float* center,
@@ -3400,8 +3380,9 @@ int hp3d_track_hands_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uin
                                    float* confidence, int32_t* lost, int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
     if (!ctx) return HP3D_ERR_ARG;
     const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
-    return track_hands_step_impl(ctx, B, H, W, K, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                                 keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, valid, area, claimed, true, &nv);
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, &nv, hand_side, true},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 
 int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
@@ -3453,12 +3434,12 @@ int hp3d_track_seed(hp3d_ctx* ctx, int B, int H, int W, const float* center, con
     HIPCHK(ctx, hipSetDevice(ctx->device));
     CHK(ensure_track(ctx, B));
     TrackState& T = ctx->track;
-    if (T.pending) { HIPCHK(ctx, hipEventSynchronize(T.ev_lost)); T.pending = false; }
+    CHK(T.h_lost.wait(ctx));
     HIPCHK(ctx, hipMemcpyAsync(T.center[T.cur], center, sizeof(float) * (size_t)B * 2, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(T.scale[T.cur], scale, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(T.lost, 0, sizeof(int) * (size_t)B, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; ++b) T.h_lost[b] = 0;
+    for (int b = 0; b < B; ++b) T.h_lost.h[b] = 0;
     T.valid = true; T.B = B; T.H = H; T.W = W; T.f = ctx->detect_scale; T.since = 0;
     return 0;
 }
@@ -3468,16 +3449,18 @@ int hp3d_track_step(hp3d_ctx* ctx, int B, int H, int W, const float* image, cons
                     int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return track_step_impl(ctx, B, H, W, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false);
+    return track_step_impl(ctx, B, H, W, StepIn{image, nullptr, nullptr, hand_side, false},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
 }
 int hp3d_track_step_dev(hp3d_ctx* ctx, int B, int H, int W, const float* image, const float* hand_side, float* image_crop,
                         float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
                         int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
     if (!ctx) return HP3D_ERR_ARG;
     if (!image) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
-    return track_step_impl(ctx, B, H, W, image, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, true);
+    return track_step_impl(ctx, B, H, W, StepIn{image, nullptr, nullptr, hand_side, true},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
 }
 int hp3d_track_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* image_u8, int H, int W, const float* hand_side,
                        float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
@@ -3486,8 +3469,9 @@ int hp3d_track_step_u8(hp3d_ctx* ctx, int B, int Hin, int Win, const uint8_t* im
     if (!image_u8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (Hin != H || Win != W)
         HP3D_FAIL(ctx, HP3D_ERR_UNSUPPORTED, "tracking crops straight from the uint8 frame: the frame (%dx%d) must have the network size (%dx%d)", Hin, Win, H, W);
-    return track_step_impl(ctx, B, H, W, nullptr, image_u8, hand_side, image_crop, scale_crop, center, keypoints_scoremap,
-                           keypoint_coord3d, keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false);
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, image_u8, nullptr, hand_side, false},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
 }
 
 int hp3d_track_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
@@ -3496,8 +3480,9 @@ int hp3d_track_step_nv12(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, c
                          int32_t* detected) {
     if (!ctx) return HP3D_ERR_ARG;
     const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
-    return track_step_impl(ctx, B, H, W, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d,
-                           keypoint_hw_crop, keypoint_hw, confidence, lost, detected, false, &nv);
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, &nv, hand_side, false},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
 }
 int hp3d_track_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* y, const uint8_t* uv, int pitch, int64_t frame_stride,
                              const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
@@ -3505,8 +3490,9 @@ int hp3d_track_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* 
                              int32_t* detected) {
     if (!ctx) return HP3D_ERR_ARG;
     const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
-    return track_step_impl(ctx, B, H, W, nullptr, nullptr, hand_side, image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d,
-                           keypoint_hw_crop, keypoint_hw, confidence, lost, detected, true, &nv);
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, &nv, hand_side, true},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
 }
 
 int hp3d_track_box(hp3d_ctx* ctx, int B, int H, int W, const double* keypoint_hw, const float* score32, float margin, float* center,
