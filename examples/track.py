@@ -8,6 +8,7 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py --synthetic                  (seeded synthetic weights + frames)
     python examples/track.py --synthetic --hands 2        (up to K hands per frame, each in its own slot: DESIGN.md 4.13)
     python examples/track.py video_hd.npy --detect-scale 4   (detect on the 4 x 4 area mean, crop from the frame: DESIGN.md 4.14)
+    python examples/track.py batch.npy --hands 2 --partial-detect   (a lost hand costs its own frame's detection only: DESIGN.md 4.18)
     python examples/track.py video_hd.npy --nv12             (the frames as NV12 planes, what a decoder delivers: DESIGN.md 4.17)
 """
 import glob
@@ -31,7 +32,7 @@ if __name__ == '__main__':
                     help='with --hands K: slots without a hand cost nothing behind their box and report zeros (DESIGN.md 4.15)')
     ap.add_argument('--partial-detect', action='store_true',
                     help='a step that detects because some frames of a batch lost their hand runs HandSegNet on those frames only '
-                         '(DESIGN.md 4.16; single-hand tracking)')
+                         '(DESIGN.md 4.16; with --hands K: on the frames that lost a hand or have none to follow, DESIGN.md 4.18)')
     ap.add_argument('--nv12', action='store_true',
                     help='convert the loaded frames to NV12 planes and track on those: crop and detection frame come straight from the '
                          'planes (DESIGN.md 4.17; frames with even height and width)')
@@ -67,6 +68,7 @@ if __name__ == '__main__':
     net.engine.set_option('track_min_score', a.min_score)
     net.engine.set_option('detect_scale', str(a.detect_scale))
     net.engine.set_option('track_partial_detect', '1' if a.partial_detect else '0')
+    net.engine.set_option('track_hands_partial_detect', '1' if a.partial_detect else '0')
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
     net.track_reset()
     net.track_hands_reset()

@@ -95,6 +95,8 @@ _SIGNATURES = {
     'hp3d_downscale': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_gather_frames': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    'hp3d_track_hands_partial_index': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_int32)]),
+    'hp3d_track_hands_select_pos': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13),
     'hp3d_boxes_to_frame': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'hp3d_boxes_to_detect': (C.c_int, [_ctx, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'hp3d_mask_from_scoremap': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
@@ -731,6 +733,40 @@ class Engine(object):
         self._chk(self.lib.hp3d_gather_frames(self.h, None if u8 else _ptr(image), _ptr(image) if u8 else None, B, H, W, int(f),
                                               _ptr(idx), int(idx.size), _ptr(out)))
         return out
+
+    # -- the multi-hand tracker's partial detection (option "track_hands_partial_detect"): the per-op forms ----
+    def track_hands_partial_index(self, valid, lost):
+        """valid / lost int32 [nb,K] -> (idx [m], pos [nb], m): the frames that have a valid slot lost or no valid slot, ascending, and
+        every frame's index among them (-1: not one of them), as a partial detect step builds them on the device."""
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        lost = np.ascontiguousarray(lost, dtype=np.int32)
+        assert valid.ndim == 2 and lost.shape == valid.shape, "valid and lost must be [nb,K]"
+        nb, K = valid.shape
+        idx, pos = np.empty((nb,), np.int32), np.empty((nb,), np.int32)
+        m = C.c_int32(-1)
+        self._chk(self.lib.hp3d_track_hands_partial_index(self.h, nb, K, _ptr(valid), _ptr(lost), _ptr(idx), _ptr(pos), C.byref(m)))
+        assert np.all(idx[m.value:] == -1)
+        return idx[:m.value].copy(), pos, int(m.value)
+
+    def track_hands_select_pos(self, pos, keep, det, box_center, box_scale, valid):
+        """A partial detect step's per-slot choice: pos [nb], keep [nb,K], det = dict of the growth's dense center [m,K,2], scale,
+        valid, area, claimed [m,K] (masks_from_scoremap(keep=...)'s), the state's box_center [nb,K,2], box_scale [nb,K], valid [nb,K]
+        -> dict of center, scale, valid, detected, area, claimed per slot."""
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        keep = np.ascontiguousarray(keep, dtype=np.int32)
+        nb, K = keep.shape
+        assert pos.shape == (nb,)
+        dc, ds = _f32(det['center']).copy(), _f32(det['scale']).copy()
+        dv, da, dk = [np.ascontiguousarray(det[k], dtype=np.int32) for k in ('valid', 'area', 'claimed')]
+        m = ds.shape[0]
+        assert dc.shape == (m, K, 2) and ds.shape == dv.shape == da.shape == dk.shape == (m, K)
+        o = {'center': _f32(box_center).copy(), 'scale': _f32(box_scale).copy(), 'valid': np.array(valid, dtype=np.int32, order='C'),
+             'detected': np.empty((nb, K), np.int32), 'area': np.empty((nb, K), np.int32), 'claimed': np.empty((nb, K), np.int32)}
+        assert o['center'].shape == (nb, K, 2) and o['scale'].shape == (nb, K) and o['valid'].shape == (nb, K)
+        self._chk(self.lib.hp3d_track_hands_select_pos(self.h, nb, K, m, _ptr(pos), _ptr(keep), _ptr(dc), _ptr(ds), _ptr(dv), _ptr(da),
+                                                       _ptr(dk), *[_ptr(o[k]) for k in ('center', 'scale', 'valid', 'detected', 'area',
+                                                                                        'claimed')]))
+        return o
 
     def boxes_to_frame(self, center_d, crop_size_d, f):
         """Detection-frame boxes (center_d [...,2], crop_size_d [...]) in frame coordinates: (center, crop_size, scale)."""

@@ -286,6 +286,8 @@ struct Options {
                                     // hand only; 0: every slot runs, absent ones on their fall-back crop
     int track_partial_detect = 0;   // option "track_partial_detect": a detect step of hp3d_track_step* that only `lost` flags caused runs HandSegNet,
                                     // the soft-max and the mask growth on the lost frames only; 0: on the whole batch
+    int track_hands_partial_detect = 0;   // option "track_hands_partial_detect": the same for hp3d_track_hands_step* -- on the frames that have a valid
+                                    // slot lost or no valid slot; 0: on the whole batch
     int nv12_matrix = 0;            // option "nv12_matrix": the colour matrix of NV12 frames: 0 "bt709" (default), 1 "bt601",
                                     // 2 "bt709_full", 3 "bt601_full" (nv12_matrix_index)
 };
@@ -321,6 +323,7 @@ struct Counters {
     long hands_compact_waits = 0;                   // ... and the stream waits for a chunk's valid flags (detect steps, hp3d_infer_hands*)
     long track_partial_frames_run = 0, track_partial_frames_skipped = 0;   // option "track_partial_detect": frames of partial chunks HandSegNet ran on / did not
     long frame_gather_launches = 0;                 // ... and the launches of frame_gather_kernel (the step and hp3d_gather_frames)
+    long track_hands_partial_frames_run = 0, track_hands_partial_frames_skipped = 0;   // option "track_hands_partial_detect": the same
     long crop_nv12_launches = 0;                    // crops taken straight from an NV12 frame (either crop_and_resize*_nv12_kernel)
 };
 
@@ -375,6 +378,11 @@ struct TrackHandsState {
     float* conf = nullptr;
     int *flags = nullptr, *detected = nullptr, *area = nullptr, *claimed = nullptr;
     int* keep = nullptr;                // valid and not lost after the last step: what a detect step behind it keeps
+    // option "track_hands_partial_detect" (grown by ensure_track_hands_partial): per chunk at its frame offset, the detecting frames'
+    // indices in the chunk | a frame's dense index; keep / centre / scale of a chunk's detecting frames, dense, and the growth's claimed
+    int pcap = 0;
+    int *pidx = nullptr, *ppos = nullptr, *keep_d = nullptr, *claimed_d = nullptr;
+    float *center_d = nullptr, *scale_d = nullptr;
     HostFlags h_flags;                  // the last step's valid | lost, copied behind the step
     int cur = 0;
     bool ok = false;                    // box[cur] and the flags hold a state for (B, K, H, W)
@@ -2468,13 +2476,28 @@ int ensure_track_hands(hp3d_ctx* ctx, int n) {
     return 0;
 }
 
+// the buffers of option "track_hands_partial_detect" for n slots: only a step that can be partial asks for them
+int ensure_track_hands_partial(hp3d_ctx* ctx, int n) {
+    TrackHandsState& T = ctx->track_hands;
+    if (n <= T.pcap) return 0;
+    CHK(dev_realloc(ctx, &T.pidx, (size_t)n));
+    CHK(dev_realloc(ctx, &T.ppos, (size_t)n));
+    CHK(dev_realloc(ctx, &T.keep_d, (size_t)n));
+    CHK(dev_realloc(ctx, &T.claimed_d, (size_t)n));
+    CHK(dev_realloc(ctx, &T.center_d, (size_t)n * 2));
+    CHK(dev_realloc(ctx, &T.scale_d, (size_t)n));
+    T.pcap = n;
+    return 0;
+}
+
 void track_hands_free(hp3d_ctx* ctx) {
     TrackHandsState& T = ctx->track_hands;
     for (int i = 0; i < 2; ++i) {
         if (T.center[i]) hipFree(T.center[i]);
         if (T.scale[i]) hipFree(T.scale[i]);
     }
-    for (void* p : {(void*)T.conf, (void*)T.flags, (void*)T.detected, (void*)T.area, (void*)T.claimed, (void*)T.keep})
+    for (void* p : {(void*)T.conf, (void*)T.flags, (void*)T.detected, (void*)T.area, (void*)T.claimed, (void*)T.keep, (void*)T.pidx, (void*)T.ppos,
+                    (void*)T.keep_d, (void*)T.claimed_d, (void*)T.center_d, (void*)T.scale_d})
         if (p) hipFree(p);
     T.h_flags.free();
     T = TrackHandsState();
@@ -2486,7 +2509,9 @@ void track_hands_free(hp3d_ctx* ctx) {
 // the crop.  TRACKED step: the K crops of a frame come from the state's boxes.  Behind the crop both are infer_hands_impl's back half
 // at batch nb * K plus the per-slot box rule.  Decided on the host, before anything is enqueued, from the valid | lost flags that travel
 // behind the previous step; the whole batch detects together; absent slots run on their fall-back crop (no compaction unless option
-// "hands_compact", DESIGN.md 4.15: run_compact_back_half).
+// "hands_compact", DESIGN.md 4.15: run_compact_back_half).  Option "track_hands_partial_detect" (DESIGN.md 4.18): a detect step that
+// flags alone caused runs HandSegNet, the soft-max and the claimed growth per chunk at batch m = the chunk's frames with a valid slot lost
+// or no valid slot, on those frames (0 < m < nb: "partial"; m = 0: the chunk is enqueued as a tracked chunk; m = nb: as without it).
 int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepIn& in, const StepOut& out) {
     if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
@@ -2517,8 +2542,13 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
     CHK(need_nets(ctx, (detect ? NET_SEG : 0) | NET_POSE | NET_PRIOR | NET_VP));
     const int mb = slot_micro_batch(ctx, B, K, Hd, Wd);
     CHK(ensure_arena(ctx, mb, Hd, Wd, mb * K));
-    if (f > 1 && !dev && !in.raw()) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
+    // option "track_hands_partial_detect": only a detect step that flags alone caused (a fresh one has nothing to keep, a scheduled one
+    // is how a hand that enters any picture is found: both run whole)
+    const bool partial_step = ctx->track_hands_partial_detect && detect && !fresh && !sched;
+    // a host float32 frame is staged where the detection frame (f > 1) or the gathered frames (a partial chunk) go to d_image
+    if ((f > 1 || partial_step) && !dev && !in.raw()) CHK(ensure_stage(ctx, (size_t)mb * H * W * 3));
     CHK(ensure_track_hands(ctx, n));
+    if (partial_step) CHK(ensure_track_hands_partial(ctx, n));
     T.ok = false;                                        // a step that fails half way leaves no state behind
     T.B = B; T.K = K; T.H = H; T.W = W; T.f = f;         // (the flags' layout: lost() = flags + B K)
     if (fresh) HIPCHK(ctx, hipMemsetAsync(T.keep, 0, sizeof(int) * (size_t)n, ctx->stream));      // nothing to keep
@@ -2530,11 +2560,59 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
         const int nb = std::min(mb, B - b0), ns = nb * K;
         const size_t s0 = (size_t)b0 * K;
         prof.chunk(b0);
-        CHK(fr.chunk(ctx, b0, nb, K, f > 1));
+        int m = nb;                                      // the chunk's frames that detect
+        if (partial_step) {
+            m = 0;
+            for (int b = b0; b < b0 + nb; ++b) {
+                bool any_valid = false, lost = false;
+                for (int j = 0; j < K; ++j) {
+                    const bool v = T.h_flags.h[b * K + j] != 0;
+                    any_valid = any_valid || v;
+                    lost = lost || (v && T.h_flags.h[n + b * K + j] != 0);
+                }
+                m += (lost || !any_valid) ? 1 : 0;
+            }
+        }
+        const bool partial = partial_step && m > 0 && m < nb;
+        const bool chunk_detect = detect && m > 0;       // (m = 0: another chunk holds the loss; this one runs as a tracked chunk)
+        CHK(fr.chunk(ctx, b0, nb, K, f > 1 || partial));
         FrameSrc crop_src = fr.src;
         float* bc = T.center[cur] + s0 * 2;
         float* bs = T.scale[cur] + s0;
-        if (detect) {
+        if (partial) {           // idx / pos from the flags, which this chunk's select and box rule have not overwritten yet
+            int* pidx = T.pidx + b0;
+            int* ppos = T.ppos + b0;
+            {
+                ProfScope ps(ctx, "track_hands_partial_index", "track_hands_partial_index", 0.0, 8.0 * ns + 8.0 * nb);
+                track_hands_partial_index_launch(T.valid() + s0, T.lost() + s0, nb, K, pidx, ppos, ctx->stream);
+            }
+            ctx->track_hands_partial_frames_run += m;
+            ctx->track_hands_partial_frames_skipped += nb - m;
+            MaskKeep mk;         // keep and the boxes of the m * K slots, dense: what the claimed growth at batch m reads
+            mk.keep = T.keep_d; mk.center = T.center_d; mk.scale = T.scale_d; mk.claimed = T.claimed_d;
+            {
+                ProfScope ps(ctx, "track_hands_slot_gather", "track_hands_slot_gather", 0.0, 32.0 * m * K);
+                track_hands_slot_gather_launch(pidx, m, K, T.keep + s0, bc, bs, T.keep_d, T.center_d, T.scale_d, ctx->stream);
+            }
+            // the m frames, dense, into d_image: never the buffer the chunk's frames lie in (a host frame was staged in d_stage)
+            if (f > 1) {
+                CHK(run_detect_reduced(ctx, fr.src, m, H, W, Hd, Wd, K, mk, pidx));
+            } else {
+                if (in.raw()) {
+                    CHK(normalise_frames(ctx, fr.src, pidx, m, H, W));
+                } else {
+                    ProfScope ps(ctx, "frame_gather", "frame_gather", 0.0, 8.0 * m * H * W * 3);
+                    frame_gather_launch(fr.src.f32, pidx, m, (size_t)H * W * 3, ctx->d_image, ctx->stream);
+                    ++ctx->frame_gather_launches;
+                }
+                HIPCHK(ctx, hipGetLastError());
+                CHK(run_detect_and_crop(ctx, ctx->d_image, m, H, W, 0, true, false, K, mk));
+            }
+            ProfScope ps(ctx, "track_hands_select_pos", "track_hands_select_pos", 0.0, 4.0 * nb + 44.0 * ns);
+            track_hands_select_pos_launch(ppos, nb, K, T.keep + s0, ctx->d_center, ctx->d_scale, ctx->d_valid, ctx->d_area, T.claimed_d, bc, bs,
+                                          T.valid() + s0, T.detected + s0, T.area + s0, T.claimed + s0, ctx->stream);
+            // (a raw frame: all nb * K crops straight from it = normalise, then crop, bit for bit)
+        } else if (chunk_detect) {
             MaskKeep mk;
             mk.keep = T.keep + s0; mk.center = bc; mk.scale = bs; mk.claimed = T.claimed + s0;
             CHK(run_detect_front(ctx, fr.src, nb, H, W, Hd, Wd, K, mk, &crop_src));
@@ -2545,9 +2623,9 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
         HIPCHK(ctx, hipGetLastError());
         const StepOut o = out.at(s0);
         // the state a tracked step's box rule also clears (a detect step's select has written it)
-        int* detected0 = detect ? nullptr : T.detected + s0;
-        int* area0 = detect ? nullptr : T.area + s0;
-        int* claimed0 = detect ? nullptr : T.claimed + s0;
+        int* detected0 = chunk_detect ? nullptr : T.detected + s0;
+        int* area0 = chunk_detect ? nullptr : T.area + s0;
+        int* claimed0 = chunk_detect ? nullptr : T.claimed + s0;
         bool compacted = false;          // option "hands_compact": the back half ran on the valid slots only and wrote its outputs
         if (ctx->hands_compact) {
             const std::function<void(const double*, const int*)> box = [&](const double* kp_dense, const int* d_pos) {
@@ -2558,7 +2636,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
             };
             // (a tracked step: the state's flags are on the host already)
             CompactChunk cc{nb, K, H, W, T.h_flags.h + s0, crop_src, bc, bs, fr.d_hs, o, dev, true, &box};
-            if (detect) CHK(compact_wait_flags(ctx, T.valid() + s0, ns, &cc.h_valid));
+            if (chunk_detect) CHK(compact_wait_flags(ctx, T.valid() + s0, ns, &cc.h_valid));
             CHK(run_compact_back_half(ctx, cc, &compacted));
         }
         if (!compacted) {
@@ -2905,6 +2983,11 @@ int hp3d_set_option(hp3d_ctx* ctx, const char* key, const char* value) {
     if (k == "hands_compact") {
         if (v != "0" && v != "1") HP3D_FAIL(ctx, HP3D_ERR_ARG, "hands_compact wants 0 or 1, got %s", value);
         ctx->hands_compact = v == "1";
+        return 0;
+    }
+    if (k == "track_hands_partial_detect") {
+        if (v != "0" && v != "1") HP3D_FAIL(ctx, HP3D_ERR_ARG, "track_hands_partial_detect wants 0 or 1, got %s", value);
+        ctx->track_hands_partial_detect = v == "1";
         return 0;
     }
     if (k == "track_partial_detect") {
@@ -3644,6 +3727,75 @@ int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u
     return finish_op(ctx);
 }
 
+// ---- the multi-hand tracker's detection on the frames that lost a hand only: the per-op forms ------------------
+int hp3d_track_hands_partial_index(hp3d_ctx* ctx, int nb, int K, const int32_t* valid, const int32_t* lost, int32_t* idx, int32_t* pos,
+                                   int32_t* m) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!valid || !lost || !idx || !pos || !m || nb < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t ns = (size_t)nb * K;
+    int32_t* d_v = S.upload(valid, ns); NN(ctx, d_v);
+    int32_t* d_l = S.upload(lost, ns); NN(ctx, d_l);
+    int32_t* d_i = S.alloc<int32_t>((size_t)nb); NN(ctx, d_i);
+    int32_t* d_p = S.alloc<int32_t>((size_t)nb); NN(ctx, d_p);
+    HIPCHK(ctx, hipMemsetAsync(d_i, 0xff, sizeof(int32_t) * (size_t)nb, ctx->stream));          // (the kernel writes idx[0 .. m) only: the rest reads -1)
+    track_hands_partial_index_launch(d_v, d_l, nb, K, d_i, d_p, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(idx, d_i, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(pos, d_p, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+    CHK(finish_op(ctx));
+    int n = 0;          // (from what the device wrote, not from the flags)
+    while (n < nb && idx[n] >= 0) ++n;
+    *m = n;
+    return 0;
+}
+
+int hp3d_track_hands_select_pos(hp3d_ctx* ctx, int nb, int K, int m, const int32_t* pos, const int32_t* keep, const float* det_center,
+                                const float* det_scale, const int32_t* det_valid, const int32_t* det_area, const int32_t* det_claimed,
+                                float* box_center, float* box_scale, int32_t* valid, int32_t* detected, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!pos || !keep || !box_center || !box_scale || !valid || !detected || !area || !claimed || nb < 1 || m < 0 || m > nb)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (m > 0 && (!det_center || !det_scale || !det_valid || !det_area || !det_claimed)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad arguments");
+    if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
+    for (int b = 0; b < nb; ++b)
+        if (pos[b] < -1 || pos[b] >= m) HP3D_FAIL(ctx, HP3D_ERR_ARG, "pos[%d] = %d is no dense index of %d", b, (int)pos[b], m);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    const size_t ns = (size_t)nb * K, nd = (size_t)std::max(m, 1) * K;
+    int32_t* d_p = S.upload(pos, (size_t)nb); NN(ctx, d_p);
+    int32_t* d_k = S.upload(keep, ns); NN(ctx, d_k);
+    float* d_dc = S.alloc<float>(nd * 2); NN(ctx, d_dc);
+    float* d_ds = S.alloc<float>(nd); NN(ctx, d_ds);
+    int32_t* d_dv = S.alloc<int32_t>(nd); NN(ctx, d_dv);
+    int32_t* d_da = S.alloc<int32_t>(nd); NN(ctx, d_da);
+    int32_t* d_dk = S.alloc<int32_t>(nd); NN(ctx, d_dk);
+    if (m > 0) {
+        const size_t md = (size_t)m * K;
+        HIPCHK(ctx, hipMemcpyAsync(d_dc, det_center, sizeof(float) * md * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_ds, det_scale, sizeof(float) * md, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_dv, det_valid, sizeof(int32_t) * md, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_da, det_area, sizeof(int32_t) * md, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_dk, det_claimed, sizeof(int32_t) * md, hipMemcpyHostToDevice, ctx->stream));
+    }
+    // box_center / box_scale / valid are read first: a slot that keeps them must get them back untouched
+    float* d_c = S.upload(box_center, ns * 2); NN(ctx, d_c);
+    float* d_s = S.upload(box_scale, ns); NN(ctx, d_s);
+    int32_t* d_v = S.upload(valid, ns); NN(ctx, d_v);
+    int32_t* d_d = S.alloc<int32_t>(ns); NN(ctx, d_d);
+    int32_t* d_a = S.alloc<int32_t>(ns); NN(ctx, d_a);
+    int32_t* d_cl = S.alloc<int32_t>(ns); NN(ctx, d_cl);
+    track_hands_select_pos_launch(d_p, nb, K, d_k, d_dc, d_ds, d_dv, d_da, d_dk, d_c, d_s, d_v, d_d, d_a, d_cl, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(box_center, d_c, sizeof(float) * ns * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(box_scale, d_s, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(valid, d_v, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(detected, d_d, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(area, d_a, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(claimed, d_cl, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
 // ---- NV12 frames: the per-op forms ---------------------------------------------------------------------------
 // Host planes at the caller's pitch and stride -> the same layout on the device (the kernels run on the pitch they were given); only
 // bytes [0, W) of a row are read on the host too: the rows are placed into a zeroed span that is then uploaded.
@@ -4229,6 +4381,8 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"hands_compact_waits", &Counters::hands_compact_waits, false},
         {"track_partial_frames_run", &Counters::track_partial_frames_run, false},
         {"track_partial_frames_skipped", &Counters::track_partial_frames_skipped, false},
+        {"track_hands_partial_frames_run", &Counters::track_hands_partial_frames_run, false},
+        {"track_hands_partial_frames_skipped", &Counters::track_hands_partial_frames_skipped, false},
         {"frame_gather_launches", &Counters::frame_gather_launches, false},
         {"crop_nv12_launches", &Counters::crop_nv12_launches, false},
     };

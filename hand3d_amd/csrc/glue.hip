@@ -2076,6 +2076,86 @@ void track_select_pos_kernel(const int* lost_prev, const int* pos, const float* 
     }
 }
 
+// ---- the multi-hand tracker's detection on the frames that lost a hand only (option "track_hands_partial_detect") ------
+// A frame detects when one of its K slots is valid and lost, or when none is valid.  idx [m] = those frames' indices in the chunk,
+// ascending; pos [n] = a frame's dense index, -1 for a frame whose slots all keep what they have.
+//
+// track_partial_index_kernel with the frame's flag reduced from its K valid | lost pairs first: ONE workgroup, n frames 256 at a time,
+// the same inclusive scan in LDS and the same running count.
+HP3D_KERNEL(256)
+void track_hands_partial_index_kernel(const int* valid, const int* lost, int n, int K, int* idx, int* pos) {
+    __shared__ int part[256];
+    const int t = threadIdx.x;
+    int base = 0;
+    for (int b0 = 0; b0 < n; b0 += 256) {          // (uniform trip count: every lane reaches every barrier)
+        const int b = b0 + t;
+        int flag = 0;
+        if (b < n) {
+            bool any_valid = false, any_lost = false;
+            for (int j = 0; j < K; ++j) {
+                const bool v = valid[b * K + j] != 0;
+                any_valid = any_valid || v;
+                any_lost = any_lost || (v && lost[b * K + j] != 0);
+            }
+            flag = (any_lost || !any_valid) ? 1 : 0;
+        }
+        part[t] = flag;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const int v = t >= d ? part[t - d] : 0;
+            __syncthreads();
+            part[t] += v;
+            __syncthreads();
+        }
+        const int incl = part[t], tot = part[255];
+        if (b < n) {
+            const int p = base + incl - 1;
+            pos[b] = flag ? p : -1;
+            if (flag) idx[p] = b;
+        }
+        base += tot;
+        __syncthreads();          // part is rewritten by the next tile
+    }
+}
+
+// keep / centre / scale of the K slots of the m frames idx[i] as dense [m, K] arrays for the claimed growth at batch m: latency only
+HP3D_KERNEL(256)
+void track_hands_slot_gather_kernel(const int* idx, int m, int K, const int* keep, const float* center, const float* scale, int* keep_d,
+                                    float* center_d, float* scale_d) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m * K; i += gridDim.x * blockDim.x) {
+        const int s = idx[i / K] * K + i % K;
+        keep_d[i] = keep[s];
+        center_d[i * 2] = center[s * 2]; center_d[i * 2 + 1] = center[s * 2 + 1];
+        scale_d[i] = scale[s];
+    }
+}
+
+// track_hands_select_kernel where the claimed growth ran on the frames of idx only: the det_* arrays are dense [m, K], frame b's K entries
+// at pos[b].  A slot of a frame with pos[b] < 0 keeps its box and its valid flag and gets detected = area = claimed = 0 (no object was
+// looked for in that frame); the `claimed` counts of the others go back to their slots.
+HP3D_KERNEL(256)
+void track_hands_select_pos_kernel(const int* pos, int nb, int K, const int* keep, const float* det_center, const float* det_scale,
+                                   const int* det_valid, const int* det_area, const int* det_claimed, float* box_center, float* box_scale,
+                                   int* valid, int* detected, int* area, int* claimed) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nb * K; i += gridDim.x * blockDim.x) {
+        const int p = pos[i / K];
+        if (p < 0) {
+            detected[i] = 0; area[i] = 0; claimed[i] = 0;
+            continue;
+        }
+        const int d = p * K + i % K;
+        claimed[i] = det_claimed[d];
+        if (keep[i]) {
+            valid[i] = 1; detected[i] = 0; area[i] = 0;
+        } else {
+            const int v = det_valid[d] != 0 ? 1 : 0;
+            box_center[i * 2] = det_center[d * 2]; box_center[i * 2 + 1] = det_center[d * 2 + 1];
+            box_scale[i] = det_scale[d];
+            valid[i] = v; detected[i] = v; area[i] = v ? det_area[d] : 0;
+        }
+    }
+}
+
 inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
     long g = (total + block - 1) / block;
     if (g < 1) g = 1;
@@ -2346,6 +2426,21 @@ void track_select_pos_launch(const int* lost_prev, const int* pos, const float* 
                              float* box_center, float* box_scale, int* detected, hipStream_t s) {
     HP3D_LAUNCH(track_select_pos_kernel, dim3(grid_for(B)), dim3(256), 0, s, lost_prev, pos, det_center, det_scale, B, box_center,
                 box_scale, detected);
+}
+void track_hands_partial_index_launch(const int* valid, const int* lost, int n, int K, int* idx, int* pos, hipStream_t s) {
+    HP3D_LAUNCH(track_hands_partial_index_kernel, dim3(1), dim3(256), 0, s, valid, lost, n, K, idx, pos);
+}
+void track_hands_slot_gather_launch(const int* idx, int m, int K, const int* keep, const float* center, const float* scale, int* keep_d,
+                                    float* center_d, float* scale_d, hipStream_t s) {
+    if (m < 1) return;
+    HP3D_LAUNCH(track_hands_slot_gather_kernel, dim3(grid_for((long)m * K)), dim3(256), 0, s, idx, m, K, keep, center, scale, keep_d,
+                center_d, scale_d);
+}
+void track_hands_select_pos_launch(const int* pos, int nb, int K, const int* keep, const float* det_center, const float* det_scale,
+                                   const int* det_valid, const int* det_area, const int* det_claimed, float* box_center, float* box_scale,
+                                   int* valid, int* detected, int* area, int* claimed, hipStream_t s) {
+    HP3D_LAUNCH(track_hands_select_pos_kernel, dim3(grid_for((long)nb * K)), dim3(256), 0, s, pos, nb, K, keep, det_center, det_scale,
+                det_valid, det_area, det_claimed, box_center, box_scale, valid, detected, area, claimed);
 }
 // T = float | unsigned char; the wide form where f is 2, 4 or 8 and every window row starts on the load's alignment
 template <typename T>

@@ -487,6 +487,17 @@ void downscale_idx_launch(const float* img, const int* idx, int m, int H, int W,
 void downscale_u8_idx_launch(const unsigned char* img, const int* idx, int m, int H, int W, int f, float* out, hipStream_t s);
 void track_select_pos_launch(const int* lost_prev, const int* pos, const float* det_center, const float* det_scale, int B,
                              float* box_center, float* box_scale, int* detected, hipStream_t s);
+// the same for the multi-hand tracker (option "track_hands_partial_detect"), K slots per frame.  A frame detects when a
+// valid slot of it is lost or none is valid: idx [m] / pos [n] over the chunk's n FRAMES, built by one workgroup from valid / lost [n,K].
+// track_hands_slot_gather: keep / center / scale of the K slots of the frames idx[i] -> dense [m,K] arrays.  track_hands_select_pos:
+// track_hands_select with dense det_* [m,K], frame b's entries at pos[b]; a slot of a frame with pos[b] < 0 keeps box and valid and gets
+// detected = area = claimed = 0; det_claimed goes back to the slots of the others.
+void track_hands_partial_index_launch(const int* valid, const int* lost, int n, int K, int* idx, int* pos, hipStream_t s);
+void track_hands_slot_gather_launch(const int* idx, int m, int K, const int* keep, const float* center, const float* scale, int* keep_d,
+                                    float* center_d, float* scale_d, hipStream_t s);
+void track_hands_select_pos_launch(const int* pos, int nb, int K, const int* keep, const float* det_center, const float* det_scale,
+                                   const int* det_valid, const int* det_area, const int* det_claimed, float* box_center, float* box_scale,
+                                   int* valid, int* detected, int* area, int* claimed, hipStream_t s);
 // compaction of absent hand slots (option "hands_compact").  idx [m]: the slots that run, ascending; pos [ns]: a slot's
 // dense index or -1.  Crop i is cut from image idx[i] / K with box idx[i] of the slot-layout center / scale and lands at dense
 // position i (the tap arithmetic of crop_and_resize_kernel / crop_and_resize_u8_kernel, op by op).

@@ -219,7 +219,7 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
-    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None, nv12_matrix=None):
+    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None, nv12_matrix=None, partial_detect=None):
         """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
             keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
             A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
@@ -231,10 +231,16 @@ class ColorHandPose3DNetwork(object):
             tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track().
             `compact`: as for inference_hands() -- a slot with valid = 0 costs nothing behind its box and returns zeros there and
             confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags.
-            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track(). """
+            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track().
+            `partial_detect` = True / False sets the engine option "track_hands_partial_detect", which stays set (None: as it is): a
+            step that detects because some frames of the batch lost a hand (or have none to follow) runs HandSegNet on those frames
+            only; every slot of the other frames keeps what it has -- a slot without a hand there is filled by the next scheduled
+            (`track_redetect`) or whole detect step, not by this one. """
         self._detect_scale(detect_scale)
         self._compact(compact)
         self._nv12_matrix(nv12_matrix)
+        if partial_detect is not None:
+            self.engine.set_option('track_hands_partial_detect', '1' if partial_detect else '0')
         planes = self._nv12_planes(image)
         if planes is not None:
             o = self.engine.track_hands_step_nv12(planes[0], planes[1], hand_side, max_hands)

@@ -157,6 +157,11 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            HandSegNet, the soft-max and the mask growth on the lost frames only, at batch m = their number per chunk; see
  *                            "partial detection" below.  "0": every call enqueues what it did without the option.  Anything else:
  *                            HP3D_ERR_ARG.  hp3d_track_hands_step* and every hp3d_infer_* call IGNORE the option;
+ *          "track_hands_partial_detect" = "0" (default) | "1": the same for hp3d_track_hands_step / _dev / _u8 / _nv12 / _nv12_dev: a detect
+ *                            step that flags alone caused runs HandSegNet, the soft-max and the claimed multi-hand growth on the frames that
+ *                            have a valid slot lost or no valid slot, at batch m = their number per chunk; see "partial detection, several
+ *                            hands" below.  "0": every call enqueues what it did without the option.  Anything else: HP3D_ERR_ARG.
+ *                            hp3d_infer_hands*, hp3d_track_step* and every hp3d_infer_* call IGNORE the option;
  *          "detect_scale" = "1" (default) | "2" ... "8", an integer f: the DETECT steps of hp3d_track_step* / hp3d_track_hands_step* find the
  *                            hand on the frame's f x f area mean ([ceil(H/f), ceil(W/f)], at least 16 x 16: HP3D_ERR_ARG before any launch
  *                            otherwise) and crop from the frame itself; see "detection on a reduced frame" below.  "1": detect on the
@@ -395,6 +400,52 @@ int hp3d_boxes_to_detect(hp3d_ctx* ctx, int n, int f, const float* center, const
  *                     Anything else: HP3D_ERR_ARG before any launch.                                                              */
 int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u8, int B, int H, int W, int f, const int32_t* idx, int m,
                        float* out);
+
+/* ---- partial detection, several hands (option "track_hands_partial_detect" = "1") ----
+ * hp3d_track_hands_step / _dev / _u8 / _nv12 / _nv12_dev only ("tracking several hands per frame" below).  Which steps detect is
+ * unchanged.  A fresh step runs whole (there is nothing to keep) and so does a scheduled one (option "track_redetect": it is how a hand
+ * that enters any picture is found).  Only a detect step that flags alone caused -- a valid slot lost, or an image with no valid slot --
+ * can be partial.  Per chunk of nb frames (at most micro_batch / K, as always), with L = the chunk's frames that have a valid slot
+ * flagged lost or no valid slot at all, ascending, m = |L|:
+ *  - m = nb: the chunk runs as without the option (same launches, same bits).
+ *  - m = 0 (another chunk holds the loss): the chunk is enqueued as a tracked chunk -- no HandSegNet, soft-max or growth; detected = area
+ *    = claimed = 0.
+ *  - 0 < m < nb: the m frames go dense to HandSegNet (as under "track_partial_detect": a copy, the normalisation of a uint8 / NV12 frame,
+ *    or at "detect_scale" = f > 1 the indexed area mean); keep, box centre and box scale of their m K slots go dense; at f > 1 those
+ *    boxes go to the detection frame; HandSegNet, the soft-max and the claimed multi-hand growth run at batch m; at f > 1 the boxes come
+ *    back to the frame; then one select writes all nb K slots, the crop of all nb K slots is taken from the full frame (a uint8 / NV12
+ *    frame: straight from it) and PoseNet2D, lifting, keypoint detection and the box rule run at batch nb K as always.
+ * What is guaranteed:
+ *  - A frame of L gets, bit for bit, what hp3d_masks_from_scoremap_keep gives on hp3d_handsegnet of a batch made of those m frames with
+ *    their own keep flags and boxes (at f > 1: hp3d_downscale* -> hp3d_handsegnet -> hp3d_boxes_to_detect -> hp3d_masks_from_scoremap_keep
+ *    -> hp3d_boxes_to_frame), and then the per-slot choice of a detect step: a kept slot holds its tracked box, the others take the
+ *    growth's; `claimed` is the growth's.  It agrees with the option-off step to the end-to-end tolerances only: HandSegNet's kernel
+ *    plan follows m.
+ *  - A kept slot of a frame outside L holds its tracked box, valid = 1, detected = area = claimed = 0, and every output of it but
+ *    `claimed` is bit-equal to the same step with the option off (without "hands_compact": the back half runs at nb K either way).
+ *  - An ABSENT slot of a frame outside L stays absent: the fall-back box, valid = 0, detected = area = claimed = 0.  THE ONE POLICY
+ *    DIFFERENCE: the whole-batch step looks at that frame too and may put a newly found object into the slot (and counts in `claimed`
+ *    the objects the frame's kept slots claim); the partial step does not look at that frame.  A hand that enters such a frame is found
+ *    by the next scheduled or whole detect step -- callers who need it soon set "track_redetect".
+ * The step is a detect step like any other: HandSegNet weights, one count in "track_hands_detect_steps" (and "detect_scale_steps"), the
+ * schedule of "track_redetect" restarts.  The lists are built on the device from the flags the previous step left there; the host
+ * learns m from its own copy of the same flags: no wait is added and nothing is read back.  With "hands_compact" = "1" the compacted back
+ * half runs behind the select exactly as behind a whole chunk's (its one wait per detecting chunk included); a chunk with m = 0 takes its
+ * flags from the host like a tracked step's.
+ * Profile rows "track_hands_partial_index", "track_hands_slot_gather", "track_hands_select_pos" (and "frame_gather" / "preprocess_u8_idx"
+ * / "preprocess_nv12_idx" / "downscale_idx" / "downscale_u8_idx" / "downscale_nv12_idx"); counters "track_hands_partial_frames_run" /
+ * "track_hands_partial_frames_skipped" (frames of partial chunks) and "frame_gather_launches".  The per-op forms (host pointers):
+ * hp3d_track_hands_partial_index  valid [nb,K], lost [nb,K] int32 -> idx [nb] (the frames of L ascending, then -1), pos [nb] (a frame's
+ *                     index in L or -1), *m = |L| as the device counted it.
+ * hp3d_track_hands_select_pos     pos [nb] in -1 ... m-1, keep [nb,K], the growth's dense results det_center [m,K,2] / det_scale /
+ *                     det_valid / det_area / det_claimed [m,K] (may be NULL when m = 0) -> box_center [nb,K,2], box_scale [nb,K], valid
+ *                     [nb,K] (all three are read first: a slot that keeps its own gets it back untouched), detected, area, claimed
+ *                     [nb,K].                                                                                                   */
+int hp3d_track_hands_partial_index(hp3d_ctx* ctx, int nb, int K, const int32_t* valid, const int32_t* lost, int32_t* idx, int32_t* pos,
+                                   int32_t* m);
+int hp3d_track_hands_select_pos(hp3d_ctx* ctx, int nb, int K, int m, const int32_t* pos, const int32_t* keep, const float* det_center,
+                                const float* det_scale, const int32_t* det_valid, const int32_t* det_area, const int32_t* det_claimed,
+                                float* box_center, float* box_scale, int32_t* valid, int32_t* detected, int32_t* area, int32_t* claimed);
 
 /* ---- compaction of absent hand slots (option "hands_compact" = "1") -------------
  * Per chunk of frames (at most micro_batch / K), idx[0 .. m) = the slots b K + j with valid = 1, ascending: the state's flags on a tracked
@@ -680,6 +731,8 @@ int hp3d_get_timing(hp3d_ctx* ctx, float* ms_per_stage, int n);
  * "track_partial_frames_run" / "track_partial_frames_skipped" = frames of hp3d_track_step* chunks that ran partially under option
  * "track_partial_detect" = "1" (0 < m < nb) on which HandSegNet ran / did not run, "frame_gather_launches" = launches of the float32 frame
  * gather (those chunks at "detect_scale" = 1 on float32 frames; hp3d_gather_frames on float32 frames at f = 1);
+ * "track_hands_partial_frames_run" / "track_hands_partial_frames_skipped" = the same for hp3d_track_hands_step* chunks under option
+ * "track_hands_partial_detect" = "1" (their float32 gathers count in "frame_gather_launches" too);
  * "conv_first_launches" = conv1_1-shaped layers (3x3, 3 -> 64) that ran on conv_first.hip;
  * "conv_wino_launches" = float32 layers that ran on conv_wino.hip (F(2x2,3x3), option "conv_impl" = "winograd" or the executor's choice);
  * "conv_mfma_launches" = layers that ran on the general direct kernel conv_mfma.hip (float32 and half precision);
