@@ -10,6 +10,7 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py video_hd.npy --detect-scale 4   (detect on the 4 x 4 area mean, crop from the frame: DESIGN.md 4.14)
     python examples/track.py batch.npy --hands 2 --partial-detect   (a lost hand costs its own frame's detection only: DESIGN.md 4.18)
     python examples/track.py video_hd.npy --nv12             (the frames as NV12 planes, what a decoder delivers: DESIGN.md 4.17)
+    python examples/track.py video_hd.npy --pixel-format bgra   (the frames as packed BGRA, what a capture surface holds: DESIGN.md 4.19)
 """
 import glob
 import json
@@ -38,12 +39,17 @@ if __name__ == '__main__':
                          'planes (DESIGN.md 4.17; frames with even height and width)')
     ap.add_argument('--nv12-matrix', default='bt709', choices=('bt709', 'bt601', 'bt709_full', 'bt601_full'),
                     help='the colour matrix of --nv12, both ways (default bt709: HD video)')
+    ap.add_argument('--pixel-format', default=None, metavar='FMT', choices=('rgb', 'bgr', 'rgba', 'bgra', 'argb', 'abgr'),
+                    help='re-lay the loaded frames as packed 8-bit pixels in this byte order and track on those: crop and detection '
+                         'frame come straight from them (DESIGN.md 4.19); not with --nv12')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
     a = ap.parse_args()
     if not a.synthetic and not a.frames:
         ap.error('give a directory of frames or a .npy file (or --synthetic)')
+    if a.nv12 and a.pixel_format:
+        ap.error('--nv12 and --pixel-format name two different frame layouts: give one')
     from hand3d_amd import synth
     from hand3d_amd.nets.ColorHandPose3DNetwork import ColorHandPose3DNetwork
 
@@ -77,13 +83,16 @@ if __name__ == '__main__':
     if a.nv12:
         from hand3d_amd.utils.nv12 import rgb_to_nv12
         net.engine.set_option('nv12_matrix', a.nv12_matrix)
+    if a.pixel_format:
+        from hand3d_amd.utils.pixels import from_rgb
+    track_kw = {'pixel_format': a.pixel_format} if a.pixel_format else {}
     for i, frame in enumerate(frames):
         frame = np.asarray(frame)
-        if a.nv12:           # (a video source hands the planes over as they are; here they are made from the loaded frame)
+        if a.nv12 or a.pixel_format:   # (a video source hands its frames over as they are; here they are made from the loaded frame)
             if frame.dtype != np.uint8:
                 frame = (frame + 0.5) * 255.0 if a.float_range == 'normalised' else frame
                 frame = np.clip(np.floor(np.asarray(frame, np.float64) + 0.5), 0, 255).astype(np.uint8)
-            image_v = rgb_to_nv12(frame[None], a.nv12_matrix)
+            image_v = rgb_to_nv12(frame[None], a.nv12_matrix) if a.nv12 else from_rgb(frame[None], a.pixel_format)
         elif frame.dtype == np.uint8:
             image_v = frame[None]                      # tracked steps crop straight from the uint8 frame
         elif a.float_range == '255':
@@ -92,7 +101,8 @@ if __name__ == '__main__':
             image_v = frame[None].astype(np.float32)
         ndet = net.engine.counter('track_hands_detect_steps')
         if a.hands:
-            coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands, compact=a.compact)
+            coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands, compact=a.compact,
+                                                                                               **track_kw)
             print(json.dumps({'frame': i, 'step': 'detect' if net.engine.counter('track_hands_detect_steps') > ndet else 'tracked',
                               'slots': [{'slot': k, 'valid': int(valid[0, k]), 'detected': int(detected[0, k]), 'area': int(area[0, k]),
                                          'center': center[0, k].tolist(), 'scale': float(scale[0, k]),
@@ -100,7 +110,7 @@ if __name__ == '__main__':
                                          'wrist_hw': kp_hw[0, k, 0].tolist(), 'wrist_xyz': coord3d[0, k, 0].tolist()}
                                         for k in range(a.hands)]}))
             continue
-        coord3d, kp_hw, kp_hw_crop, scale, center, confidence, lost, detected = net.track(image_v, hand_side_v)
+        coord3d, kp_hw, kp_hw_crop, scale, center, confidence, lost, detected = net.track(image_v, hand_side_v, **track_kw)
         print(json.dumps({'frame': i, 'step': 'detect' if detected[0] else 'tracked', 'center': center[0].tolist(),
                           'scale': float(scale[0, 0]), 'confidence': float(confidence[0]), 'lost': int(lost[0]),
                           'wrist_hw': kp_hw[0, 0].tolist(), 'wrist_xyz': coord3d[0, 0].tolist()}))

@@ -11,6 +11,8 @@ import weakref
 
 import numpy as np
 
+from .utils.pixels import FORMATS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'libhp3d.so')
 
@@ -86,6 +88,15 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale_nv12': (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
                                       C.c_int, C.c_void_p]),
+    'hp3d_track_step_px': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 11),
+    'hp3d_track_step_px_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 11),
+    'hp3d_track_hands_step_px': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_track_hands_step_px_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_px_to_rgb': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    'hp3d_crop_and_resize_px': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_downscale_px': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_int, C.c_void_p]),
     'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
     'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
     'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -648,6 +659,96 @@ class Engine(object):
         out = np.empty((n, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
         self._chk(self.lib.hp3d_downscale_nv12(self.h, C.c_void_p(py), C.c_void_p(puv), B, H, W, pitch, fs, int(f), _ptr(idx),
                                                0 if idx is None else int(idx.size), _ptr(out)))
+        return out
+
+    # -- packed 8-bit frames (include/hp3d.h "packed 8-bit frames") ---------------------
+    @staticmethod
+    def _px_surface(frames, pixel_format):
+        """uint8 [B,H,W,pixel_bytes] -> (keepalive, address, B, H, W, pitch, frame_stride, format).  An array whose strides fit the
+        layout (last axis 1, pixel stride = pixel_bytes, row stride >= W pixel_bytes, frame stride positive and long enough) -- a padded
+        surface, a region of interest of a wider one -- is passed as it lies, with no copy; anything else is copied once."""
+        if pixel_format not in FORMATS:
+            raise ValueError("pixel_format must be one of %s, got %r" % (', '.join(sorted(FORMATS)), pixel_format))
+        fmt, pb, _ = FORMATS[pixel_format]
+        a = np.asarray(frames)
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != pb:
+            raise ValueError("pixel_format %r wants uint8 frames [B,H,W,%d]" % (pixel_format, pb))
+        B, H, W, _ = a.shape
+        sb, sr, sp, sc = a.strides
+        in_place = sc == 1 and sp == pb and sr >= W * pb and (B == 1 or sb >= sr * (H - 1) + W * pb)
+        if not in_place:
+            a = np.ascontiguousarray(a)
+            sb, sr = a.strides[:2]
+        return a, a.ctypes.data, B, H, W, int(sr), (int(sb) if B > 1 else 0), fmt
+
+    def track_step_px(self, frames, pixel_format, hand_side, want_kpmap=False):
+        """track_step on packed 8-bit frames: uint8 [B,H,W,pixel_bytes] in `pixel_format` ('rgb', 'bgr', 'rgba', 'bgra', 'argb',
+        'abgr'), rows at any pitch (_px_surface).  Every output equals track_step_u8 on the repacked frames bit for bit."""
+        keep, p, B, H, W, pitch, fs, fmt = self._px_surface(frames, pixel_format)
+        hand_side = _f32(hand_side)
+        assert hand_side.shape == (B, 2), "hand_side must be [B,2]"
+        o = self._track_outputs(B, want_kpmap)
+        self._chk(self.lib.hp3d_track_step_px(self.h, B, H, W, C.c_void_p(p), pitch, fs, fmt, _ptr(hand_side),
+                                              *[_ptr(o[k]) for k in self._TRACK_ORDER]))
+        return o
+
+    def track_step_px_dev(self, B, H, W, px_ptr, pitch, frame_stride, pixel_format, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0,
+                          coord3d=0, kp_crop=0, kp_hw=0, confidence=0, lost=0, detected=0):
+        """Device-pointer variant (ints): the surface is read in place; stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_step_px_dev(self.h, B, H, W, v(px_ptr), int(pitch), int(frame_stride), FORMATS[pixel_format][0],
+                                                  v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap), v(coord3d), v(kp_crop), v(kp_hw),
+                                                  v(confidence), v(lost), v(detected)))
+
+    def track_hands_step_px(self, frames, pixel_format, hand_side, max_hands, want_kpmap=False):
+        """track_hands_step on packed 8-bit frames (as track_step_px); equals track_hands_step_u8 on the repacked frames bit for bit."""
+        keep, p, B, H, W, pitch, fs, fmt = self._px_surface(frames, pixel_format)
+        hand_side = _f32(hand_side)
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._track_hands_outputs(B, K, want_kpmap)
+        self._chk(self.lib.hp3d_track_hands_step_px(self.h, B, H, W, C.c_void_p(p), pitch, fs, fmt, K, _ptr(hand_side),
+                                                    *[_ptr(o[k]) for k in self._TRACK_HANDS_ORDER]))
+        return o
+
+    def track_hands_step_px_dev(self, B, H, W, K, px_ptr, pitch, frame_stride, pixel_format, hand_side_ptr, crop=0, scale=0, center=0,
+                                kpmap=0, coord3d=0, kp_crop=0, kp_hw=0, confidence=0, lost=0, detected=0, valid=0, area=0, claimed=0):
+        """Device-pointer variant (ints): the surface is read in place; stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.hp3d_track_hands_step_px_dev(self.h, B, H, W, v(px_ptr), int(pitch), int(frame_stride), FORMATS[pixel_format][0],
+                                                        int(K), v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap), v(coord3d),
+                                                        v(kp_crop), v(kp_hw), v(confidence), v(lost), v(detected), v(valid), v(area),
+                                                        v(claimed)))
+
+    def px_to_rgb(self, frames, pixel_format):
+        """Packed 8-bit frames -> uint8 RGB [B,H,W,3] (= utils.pixels.to_rgb)."""
+        keep, p, B, H, W, pitch, fs, fmt = self._px_surface(frames, pixel_format)
+        out = np.empty((B, H, W, 3), np.uint8)
+        self._chk(self.lib.hp3d_px_to_rgb(self.h, C.c_void_p(p), B, H, W, pitch, fs, fmt, _ptr(out)))
+        return out
+
+    def crop_and_resize_px(self, frames, pixel_format, center, scale, K=1, idx=None, crop_size=256):
+        """crop_and_resize straight from packed 8-bit frames: center [B*K,2], scale [B*K], K boxes per frame -> [B*K,crop,crop,3]; with
+        idx [m] (slot indices) the crops idx[i] only -> [m,crop,crop,3].  = crop_and_resize_u8 / crop_and_resize_idx on px_to_rgb."""
+        keep, p, B, H, W, pitch, fs, fmt = self._px_surface(frames, pixel_format)
+        center, scale = _f32(center).reshape(-1, 2), _f32(scale).reshape(-1)
+        assert center.shape[0] == B * int(K) and scale.shape[0] == B * int(K), "center / scale must hold B*K boxes"
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B * int(K) if idx is None else idx.size
+        out = np.empty((n, crop_size, crop_size, 3), np.float32)
+        self._chk(self.lib.hp3d_crop_and_resize_px(self.h, C.c_void_p(p), B, H, W, pitch, fs, fmt, int(K), _ptr(center), _ptr(scale),
+                                                   _ptr(idx), 0 if idx is None else int(idx.size), int(crop_size), _ptr(out)))
+        return out
+
+    def downscale_px(self, frames, pixel_format, f, idx=None):
+        """The detection frame of packed 8-bit frames [B or m,ceil(H/f),ceil(W/f),3] (f = 1: the normalised frame); idx: the frames
+        idx[i] only.  = downscale_u8 (f = 1: preprocess_u8 at equal sizes) on px_to_rgb, bit for bit."""
+        keep, p, B, H, W, pitch, fs, fmt = self._px_surface(frames, pixel_format)
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B if idx is None else idx.size
+        out = np.empty((n, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
+        self._chk(self.lib.hp3d_downscale_px(self.h, C.c_void_p(p), B, H, W, pitch, fs, fmt, int(f), _ptr(idx),
+                                             0 if idx is None else int(idx.size), _ptr(out)))
         return out
 
     def track_box(self, keypoint_hw, H, W, score32=None, margin=None):

@@ -325,6 +325,7 @@ struct Counters {
     long frame_gather_launches = 0;                 // ... and the launches of frame_gather_kernel (the step and hp3d_gather_frames)
     long track_hands_partial_frames_run = 0, track_hands_partial_frames_skipped = 0;   // option "track_hands_partial_detect": the same
     long crop_nv12_launches = 0;                    // crops taken straight from an NV12 frame (either crop_and_resize*_nv12_kernel)
+    long crop_px_launches = 0;                      // crops taken straight from a packed 8-bit frame (either crop_and_resize*_px_kernel)
 };
 
 // A page-locked int buffer that small copies fill or drain behind the stream (the trackers' flags, the compaction's maps), the event
@@ -440,6 +441,7 @@ struct hp3d_ctx : Options, Counters {
     unsigned char* d_u8 = nullptr;
     size_t u8_bytes = 0;
     std::vector<unsigned char> h_nv12;               // host NV12 planes with a pitch above W, packed tight for their upload
+    std::vector<unsigned char> h_px;                 // host packed 8-bit frames with padded rows or frames, likewise
     size_t image_floats = 0, large_floats = 0, det_bytes = 0, pose_px = 0;
 
     // profiling
@@ -1913,17 +1915,64 @@ int upload_nv12(hp3d_ctx* ctx, int B, int H, int W, const Nv12Arg& a, Nv12Src* o
     return 0;
 }
 
-// The frames of a chunk of a tracking step: float32, uint8 or NV12 -- exactly one is set.  The wrappers below switch on the kind, so
-// the three-way branch is written once; the float32 and uint8 launches, profile rows and counters are the ones they were.
+// ---- packed 8-bit frames (layout and formats: include/hp3d.h) ---------------------------------------------------------
+// What the caller handed over: frame 0's first byte (host or device pointer), the row pitch, the frame stride, the format.
+struct PxArg {
+    const unsigned char* px;
+    int pitch;
+    long long frame_stride;
+    int format;
+};
+// every refusal comes before anything is enqueued
+int check_px(hp3d_ctx* ctx, int B, int H, int W, const PxArg& a) {
+    const int pb = px_pixel_bytes(a.format);
+    if (!pb) HP3D_FAIL(ctx, HP3D_ERR_ARG, "px: format=%d is none of HP3D_PX_RGB ... HP3D_PX_ABGR (0 ... 5)", a.format);
+    if (!a.px) HP3D_FAIL(ctx, HP3D_ERR_ARG, "px: px (the surface) is NULL");
+    if (B < 1 || H < 16 || W < 16) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad shape B=%d H=%d W=%d (need B>=1, H,W >=16)", B, H, W);
+    if (a.pitch < (long long)W * pb) HP3D_FAIL(ctx, HP3D_ERR_ARG, "px: pitch=%d is below W * pixel_bytes = %lld", a.pitch, (long long)W * pb);
+    const long long need = (long long)a.pitch * (H - 1) + (long long)W * pb;
+    if (B > 1 && a.frame_stride < need)
+        HP3D_FAIL(ctx, HP3D_ERR_ARG, "px: frame_stride=%lld is below pitch * (H - 1) + W * pixel_bytes = %lld", a.frame_stride, need);
+    return 0;
+}
+// Host frames -> d_u8, packed tight at pixel_bytes bytes a pixel (the buffer is sized for 4: a stream that changes format re-allocates
+// nothing).  Only bytes [0, W pixel_bytes) of a row are read: contiguous rows and frames are ONE copy as they lie, anything else is
+// packed row by row on the host first.  A 4-byte surface always lands `wide`; the 4-to-3 gather is the kernels' job.
+int upload_px(hp3d_ctx* ctx, int B, int H, int W, const PxArg& a, PxSrc* out) {
+    const int pb = px_pixel_bytes(a.format);
+    const size_t row = (size_t)W * pb, fs = row * H, nbytes = fs * B, cap = (size_t)B * H * W * 4;
+    if (cap > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, cap)); ctx->u8_bytes = cap; }
+    const size_t stride = B > 1 ? (size_t)a.frame_stride : 0;
+    if ((size_t)a.pitch == row && (B == 1 || stride == fs)) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, a.px, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        // (the previous call's upload has completed: every host form ends on a stream synchronise)
+        ctx->h_px.resize(nbytes);
+        for (int b = 0; b < B; ++b)
+            for (int r = 0; r < H; ++r) memcpy(ctx->h_px.data() + b * fs + r * row, a.px + b * stride + (size_t)r * a.pitch, row);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_u8, ctx->h_px.data(), nbytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *out = px_src(ctx->d_u8, (int)row, B > 1 ? fs : 0, a.format);
+    return 0;
+}
+
+// The frames of a chunk of a tracking step: float32, uint8, NV12 or packed 8-bit -- exactly one is set.  The wrappers below switch on the
+// kind, so the branch is written once; the float32 and uint8 launches, profile rows and counters are the ones they were.
 struct FrameSrc {
     const float* f32 = nullptr;
     const unsigned char* u8 = nullptr;
     const Nv12Src* nv12 = nullptr;
+    const PxSrc* px = nullptr;
+    bool raw() const { return u8 || nv12 || px; }
 };
 // the nb * K crops of nb frames, K boxes per frame, into d_crop
 int crop_frames(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* bc, const float* bs) {
     const int ns = nb * K;
-    if (src.nv12) {
+    if (src.px) {
+        ProfScope ps(ctx, "crop_and_resize_px", "crop_and_resize_px", 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * ns * 256 * 256 * 3);
+        crop_and_resize_px_launch(*src.px, ns, H, W, bc, bs, nullptr, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_px_launches;
+    } else if (src.nv12) {
         ProfScope ps(ctx, "crop_and_resize_nv12", "crop_and_resize_nv12", 0.0, 1.5 * nb * H * W + 4.0 * ns * 256 * 256 * 3);
         crop_and_resize_nv12_launch(*src.nv12, ns, H, W, bc, bs, nullptr, K, 256, ctx->d_crop, ctx->stream);
         ++ctx->crop_nv12_launches;
@@ -1941,7 +1990,11 @@ int crop_frames(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W,
 // the m crops of the slots idx[i] (option "hands_compact"), dense, into d_crop
 int crop_frames_idx(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* center, const float* scale, const int* d_idx,
                     int m) {
-    if (src.nv12) {
+    if (src.px) {
+        ProfScope ps(ctx, "crop_and_resize_idx_px", "crop_and_resize_idx_px", 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * m * 256 * 256 * 3);
+        crop_and_resize_px_launch(*src.px, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_px_launches;
+    } else if (src.nv12) {
         ProfScope ps(ctx, "crop_and_resize_idx_nv12", "crop_and_resize_idx_nv12", 0.0, 1.5 * nb * H * W + 4.0 * m * 256 * 256 * 3);
         crop_and_resize_nv12_launch(*src.nv12, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
         ++ctx->crop_nv12_launches;
@@ -1958,7 +2011,11 @@ int crop_frames_idx(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, in
 }
 // a raw frame as the normalised float32 frame in d_image: all nb frames (idx null) or the frames idx[i], i < nb, dense
 int normalise_frames(hp3d_ctx* ctx, const FrameSrc& src, const int* idx, int nb, int H, int W) {
-    if (src.nv12) {
+    if (src.px) {
+        const char* row = idx ? "preprocess_px_idx" : "preprocess_px";
+        ProfScope ps(ctx, row, row, 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * nb * H * W * 3);
+        downscale_px_launch(*src.px, idx, nb, H, W, 1, ctx->d_image, ctx->stream);
+    } else if (src.nv12) {
         const char* row = idx ? "preprocess_nv12_idx" : "preprocess_nv12";
         ProfScope ps(ctx, row, row, 0.0, 1.5 * nb * H * W + 4.0 * nb * H * W * 3);
         downscale_nv12_launch(*src.nv12, idx, nb, H, W, 1, ctx->d_image, ctx->stream);
@@ -1981,7 +2038,12 @@ int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W,
     const int f = ctx->detect_scale, slots = nb * std::max(K, 1);
     const float* d_img = src.f32;
     const unsigned char* d_u8 = src.u8;
-    if (src.nv12) {
+    if (src.px) {
+        const char* row = idx ? "downscale_px_idx" : "downscale_px";
+        ProfScope ps(ctx, row, row, 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * nb * Hd * Wd * 3);
+        downscale_px_launch(*src.px, idx, nb, H, W, f, ctx->d_image, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+    } else if (src.nv12) {
         const char* row = idx ? "downscale_nv12_idx" : "downscale_nv12";
         ProfScope ps(ctx, row, row, 0.0, 1.5 * nb * H * W + 4.0 * nb * Hd * Wd * 3);
         downscale_nv12_launch(*src.nv12, idx, nb, H, W, f, ctx->d_image, ctx->stream);
@@ -2013,14 +2075,16 @@ int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W,
 }
 
 // ---- what the step functions share (hp3d_track_step*, hp3d_track_hands_step*, hp3d_infer_hands*) ----------------------------------
-// What a step was handed: the frames -- float32, uint8 (host) or NV12, exactly one is set -- and hand_side; dev: device pointers.
+// What a step was handed: the frames -- float32, uint8 (host), NV12 or packed 8-bit, exactly one is set -- and hand_side; dev: device
+// pointers.
 struct StepIn {
     const float* image = nullptr;
     const unsigned char* image_u8 = nullptr;
     const Nv12Arg* nv = nullptr;
     const float* hand_side = nullptr;
     bool dev = false;
-    bool raw() const { return image_u8 || nv; }          // uint8 or NV12 frames: no float32 frame comes in
+    const PxArg* px = nullptr;
+    bool raw() const { return image_u8 || nv || px; }    // uint8, NV12 or packed 8-bit frames: no float32 frame comes in
 };
 // Where a step's results go, one entry per slot (null: skipped); device pointers when the step's input is.
 struct StepOut {
@@ -2044,16 +2108,17 @@ int copy_out(hp3d_ctx* ctx, int32_t* dst, const int* src, size_t n, bool dev) { 
     return copy_out(ctx, (float*)dst, (const float*)src, n, dev);
 }
 
-// The frames of a tracking step on the device.  upload(), once: uint8 frames into d_u8, NV12 surfaces in place (dev) or as their packed
-// upload.  chunk(), per chunk of nb frames from b0 with K slots each: hand_side and a host float32 frame to the device, then the chunk's
+// The frames of a tracking step on the device.  upload(), once: uint8 frames into d_u8, NV12 and packed 8-bit surfaces in place (dev) or
+// as their packed upload.  chunk(), per chunk of nb frames from b0 with K slots each: hand_side and a host float32 frame to the device, then the chunk's
 // FrameSrc.  stage: the host float32 frame goes to d_stage, because the chunk puts something else into d_image (a detection frame, the
 // gathered lost frames).
 struct StepFrames {
     const StepIn& in;
     const int H, W;
     Nv12Src nvs{}, nvc{};
+    PxSrc pxs{}, pxc{};
     const float* d_hs = nullptr;          // the chunk's hand_side on the device
-    FrameSrc src;                         // the chunk's frames (src.nv12 points into this record)
+    FrameSrc src;                         // the chunk's frames (src.nv12 and src.px point into this record)
     int upload(hp3d_ctx* ctx, int B) {
         if (in.image_u8) {
             const size_t nbytes = (size_t)B * H * W * 3;
@@ -2062,6 +2127,8 @@ struct StepFrames {
         }
         if (in.nv && in.dev) nvs = nv12_src(in.nv->y, in.nv->uv, in.nv->pitch, B > 1 ? (size_t)in.nv->frame_stride : 0, ctx->nv12_matrix);
         else if (in.nv) CHK(upload_nv12(ctx, B, H, W, *in.nv, &nvs));
+        if (in.px && in.dev) pxs = px_src(in.px->px, in.px->pitch, B > 1 ? (size_t)in.px->frame_stride : 0, in.px->format);
+        else if (in.px) CHK(upload_px(ctx, B, H, W, *in.px, &pxs));
         return 0;
     }
     int chunk(hp3d_ctx* ctx, int b0, int nb, int K, bool stage) {
@@ -2081,6 +2148,8 @@ struct StepFrames {
         }
         nvc = nvs.at(b0);
         src.nv12 = in.nv ? &nvc : nullptr;
+        pxc = pxs.at(b0);
+        src.px = in.px ? &pxc : nullptr;
         return 0;
     }
 };
@@ -2099,7 +2168,7 @@ int slot_micro_batch(const hp3d_ctx* ctx, int B, int K, int H, int W) {
 int run_detect_front(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W, int Hd, int Wd, int K, const MaskKeep& mk, FrameSrc* crop_src) {
     *crop_src = src;
     if (ctx->detect_scale > 1) return run_detect_reduced(ctx, src, nb, H, W, Hd, Wd, K, mk);
-    const bool raw = src.u8 || src.nv12;
+    const bool raw = src.raw();
     if (raw) {
         CHK(normalise_frames(ctx, src, nullptr, nb, H, W));
         *crop_src = FrameSrc();
@@ -2167,6 +2236,7 @@ int copy_out_slots(hp3d_ctx* ctx, const StepOut& out, int n, const float* scale,
 int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const StepIn& in, const StepOut& out) {
     if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
+    if (in.px) CHK(check_px(ctx, B, H, W, *in.px));
     CHK(check_img(ctx, B, H, W));
     const bool dev = in.dev;
     int Hd, Wd;
@@ -2516,6 +2586,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
     if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
     if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
+    if (in.px) CHK(check_px(ctx, B, H, W, *in.px));
     CHK(check_img(ctx, B, H, W));
     const bool dev = in.dev;
     int Hd, Wd;
@@ -3468,6 +3539,27 @@ int hp3d_track_hands_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uin
                                          keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 
+int hp3d_track_hands_step_px(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format, int K,
+                             const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                             float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                             int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, nullptr, hand_side, false, &pa},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
+}
+int hp3d_track_hands_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format, int K,
+                                 const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                                 float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                                 int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, nullptr, hand_side, true, &pa},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
+}
+
 int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
                          const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
                          float* confidence, int32_t* lost) {
@@ -3574,6 +3666,27 @@ int hp3d_track_step_nv12_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* 
     if (!ctx) return HP3D_ERR_ARG;
     const Nv12Arg nv{y, uv, pitch, (long long)frame_stride};
     return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, &nv, hand_side, true},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
+}
+
+int hp3d_track_step_px(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format,
+                       const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                       float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                       int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, nullptr, hand_side, false, &pa},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
+}
+int hp3d_track_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format,
+                           const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                           float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                           int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, nullptr, hand_side, true, &pa},
                            StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
                                    confidence, lost, detected});
 }
@@ -3873,6 +3986,86 @@ int hp3d_downscale_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int 
     if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
     float* d_o = S.alloc<float>(no); NN(ctx, d_o);
     downscale_nv12_launch(src, d_i, n, H, W, f, d_o, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+// ---- packed 8-bit frames: the per-op forms ---------------------------------------------------------------------
+// A host surface at the caller's pitch and stride -> the same layout on the device, at the caller's base misalignment (modulo 16), so
+// that the kernels run on what they were given.  Only bytes [0, W pixel_bytes) of a row are read on the host: the rows are placed into
+// a span of 255s that is then uploaded.
+static int upload_px_as_is(hp3d_ctx* ctx, Scratch& S, int B, int H, int W, const PxArg& a, PxSrc* out) {
+    const size_t stride = B > 1 ? (size_t)a.frame_stride : 0, row = (size_t)W * px_pixel_bytes(a.format);
+    const size_t lead = (uintptr_t)a.px % 16, span = stride * (B - 1) + (size_t)a.pitch * (H - 1) + row;
+    std::vector<unsigned char>& h = ctx->h_px;
+    h.assign(lead + span, 255);
+    for (int b = 0; b < B; ++b)
+        for (int r = 0; r < H; ++r) memcpy(&h[lead + b * stride + (size_t)r * a.pitch], a.px + b * stride + (size_t)r * a.pitch, row);
+    unsigned char* d = S.upload(h.data(), h.size()); NN(ctx, d);
+    *out = px_src(d + lead, a.pitch, stride, a.format);
+    return 0;
+}
+int hp3d_px_to_rgb(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, uint8_t* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    CHK(check_px(ctx, B, H, W, pa));
+    if (!out) HP3D_FAIL(ctx, HP3D_ERR_ARG, "px_to_rgb: out is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    PxSrc src;
+    CHK(upload_px_as_is(ctx, S, B, H, W, pa, &src));
+    const size_t no = (size_t)B * H * W * 3;
+    unsigned char* d_o = S.alloc<unsigned char>(no); NN(ctx, d_o);
+    px_to_rgb_launch(src, B, H, W, d_o, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_crop_and_resize_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, int K,
+                            const float* center, const float* scale, const int32_t* idx, int m, int crop_size, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    CHK(check_px(ctx, B, H, W, pa));
+    if (!center || !scale || !out || K < 1 || K > HP3D_MAX_HANDS || crop_size < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_px: bad arguments");
+    if (idx && (m < 0 || m > B * K)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_px: m = %d must be in 0 ... B K = %d", m, B * K);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B * K) HP3D_FAIL(ctx, HP3D_ERR_ARG, "idx[%d] = %d is no slot of %d", i, (int)idx[i], B * K);
+    const int n = idx ? m : B * K;
+    if (n == 0) return 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    PxSrc src;
+    CHK(upload_px_as_is(ctx, S, B, H, W, pa, &src));
+    const size_t no = (size_t)n * crop_size * crop_size * 3;
+    float* d_c = S.upload(center, (size_t)B * K * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)B * K); NN(ctx, d_s);
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    crop_and_resize_px_launch(src, n, H, W, d_c, d_s, d_i, K, crop_size, d_o, ctx->stream);
+    ++ctx->crop_px_launches;
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_downscale_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, int f,
+                      const int32_t* idx, int m, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    const PxArg pa{px, pitch, (long long)frame_stride, format};
+    CHK(check_px(ctx, B, H, W, pa));
+    if (!out || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_px: bad arguments (f = %d must be in 1 ... 8)", f);
+    if (idx && (m < 1 || m > B)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_px: m = %d must be in 1 ... B = %d", m, B);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_px: idx[%d] = %d is no frame of %d", i, (int)idx[i], B);
+    const int n = idx ? m : B;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    PxSrc src;
+    CHK(upload_px_as_is(ctx, S, B, H, W, pa, &src));
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const size_t no = (size_t)n * Hd * Wd * 3;
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    downscale_px_launch(src, d_i, n, H, W, f, d_o, ctx->stream);
     HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
@@ -4385,6 +4578,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"track_hands_partial_frames_skipped", &Counters::track_hands_partial_frames_skipped, false},
         {"frame_gather_launches", &Counters::frame_gather_launches, false},
         {"crop_nv12_launches", &Counters::crop_nv12_launches, false},
+        {"crop_px_launches", &Counters::crop_px_launches, false},
     };
     const std::string k(name);
     for (const auto& c : table)

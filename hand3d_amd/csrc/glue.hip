@@ -305,6 +305,36 @@ struct TapNv12 {
         v[0] = u8_norm(p.r); v[1] = u8_norm(p.g); v[2] = u8_norm(p.b);
     }
 };
+// ---- packed 8-bit frames ----------------------------------------------------------------------------------------------
+// Pixel (r, c) of frame `fr` of a packed surface as three uint8 channels.  wide (4-byte pixels on a 4-byte grid): ONE 32-bit load, the
+// channels by shifts (byte k of a little-endian word is bits 8 k ...); otherwise three byte loads, so that a 3-byte pixel never reaches
+// past its row.  The fourth byte of a 4-byte pixel is never looked at.
+__device__ __forceinline__ Rgb8 px_unpack(const PxSrc& P, unsigned w) {
+    Rgb8 o;
+    o.r = (int)((w >> (8 * P.ro)) & 255u); o.g = (int)((w >> (8 * P.go)) & 255u); o.b = (int)((w >> (8 * P.bo)) & 255u);
+    return o;
+}
+__device__ __forceinline__ Rgb8 px_pixel(const PxSrc& P, size_t fr, int r, int c) {
+    const unsigned char* p = P.px + fr * P.frame_stride + (size_t)r * P.pitch + (size_t)c * P.pixel_bytes;
+    if (P.wide) {
+        unsigned w;
+        __builtin_memcpy(&w, __builtin_assume_aligned(p, 4), 4);
+        return px_unpack(P, w);
+    }
+    Rgb8 o;
+    o.r = p[P.ro]; o.g = p[P.go]; o.b = p[P.bo];
+    return o;
+}
+// A packed tap hands back a whole pixel, as TapNv12 does: one fetch per tap, each channel normalised as TapU8 does -- the crop equals
+// crop_and_resize_u8 on the repacked frame bit for bit.
+struct TapPx {
+    PxSrc P;
+    static constexpr bool PIXEL = true;
+    __device__ __forceinline__ void pixel(size_t fr, int r, int c, float* v) const {
+        const Rgb8 p = px_pixel(P, fr, r, c);
+        v[0] = u8_norm(p.r); v[1] = u8_norm(p.g); v[2] = u8_norm(p.b);
+    }
+};
 // the four taps of an output pixel of a PIXEL tap, interpolated as crop_and_resize_body does per channel
 template <class Tap>
 __device__ __forceinline__ void crop_pixel_taps(const Tap& tap, size_t fr, int ty0, int ty1, int tx0, int tx1, float ly, float lx, float* o) {
@@ -375,6 +405,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_nv12_kernel(const Nv12Src src, int B, int H, int W, const float* center, const float* scale, int crop, float* out,
                                  int boxes_per_image) {
     crop_and_resize_body(TapNv12{src}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_px_kernel(const PxSrc src, int B, int H, int W, const float* center, const float* scale, int crop, float* out,
+                               int boxes_per_image) {
+    crop_and_resize_body(TapPx{src}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
 }
 
 HP3D_KERNEL(256)
@@ -1831,6 +1866,107 @@ void nv12_to_rgb_kernel(const Nv12Src P, int B, int H, int W, unsigned char* out
     }
 }
 
+// The detection frame of packed 8-bit frames: one thread per output pixel, three exact unsigned sums, the uint8 frames'
+// finish -- downscale_u8 on the repacked frame bit for bit.  F > 0 (f = 2, 4, 8 with `wide`: base, pitch and frame stride multiples of the
+// load's alignment): a full window row is F pixel_bytes bytes in the fewest loads of at most 16 bytes -- 8 / 16 / 2 x 16 bytes for 4-byte
+// pixels, and for 3-byte pixels downscale_body<unsigned char, F>'s 6 / 12 / 24 bytes at 2 / 4 / 8-byte alignment, the pitch explicit.
+// A full window lies inside its row, so neither reaches past it.  Odd f, ragged windows and unaligned surfaces: pixel by pixel.
+template <int F, bool IDX>
+__device__ __forceinline__ void downscale_px_body(const PxSrc P, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
+                                                  const int* idx) {
+    constexpr int NP = F > 0 ? F : 1;
+    constexpr int A4 = NP * 4 >= 16 ? 16 : NP * 4;
+    constexpr int A3 = (NP * 3) % 8 == 0 ? 8 : (NP * 3) % 4 == 0 ? 4 : (NP * 3) % 2 == 0 ? 2 : 1;
+    const long total = (long)B * Hd * Wd;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wd);
+        long r = i / Wd;
+        const int y = (int)(r % Hd);
+        const int b = (int)(r / Hd);
+        const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
+        const size_t sb = (size_t)(IDX ? idx[b] : b);
+        unsigned s0 = 0, s1 = 0, s2 = 0;
+        bool done = false;
+        if constexpr (F > 0) if (wide && nx == F) {
+            done = true;
+            const unsigned char* p = P.px + sb * P.frame_stride + (size_t)y0 * P.pitch + (size_t)x0 * P.pixel_bytes;
+            if (P.pixel_bytes == 4) {
+                for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
+                    unsigned v[NP];
+                    __builtin_memcpy(v, __builtin_assume_aligned(p, A4), sizeof(v));
+#pragma unroll
+                    for (int k = 0; k < NP; ++k) {
+                        const Rgb8 q = px_unpack(P, v[k]);
+                        s0 += q.r; s1 += q.g; s2 += q.b;
+                    }
+                }
+            } else {          // (3-byte pixels: the sums per byte position, sorted into R, G, B once at the end)
+                unsigned t0 = 0, t1 = 0, t2 = 0;
+                for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
+                    unsigned char v[NP * 3];
+                    __builtin_memcpy(v, __builtin_assume_aligned(p, A3), sizeof(v));
+#pragma unroll
+                    for (int k = 0; k < NP * 3; k += 3) { t0 += v[k]; t1 += v[k + 1]; t2 += v[k + 2]; }
+                }
+                s0 = P.ro == 0 ? t0 : P.ro == 1 ? t1 : t2;
+                s1 = P.go == 0 ? t0 : P.go == 1 ? t1 : t2;
+                s2 = P.bo == 0 ? t0 : P.bo == 1 ? t1 : t2;
+            }
+        }
+        if (!done) {
+            for (int yy = y0; yy < y1; ++yy)
+                for (int k = 0; k < nx; ++k) {
+                    const Rgb8 q = px_pixel(P, sb, yy, x0 + k);
+                    s0 += q.r; s1 += q.g; s2 += q.b;
+                }
+        }
+        const float n = (float)((y1 - y0) * nx);
+        float* o = out + (size_t)i * 3;
+        o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
+    }
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_px_kernel(const PxSrc src, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_px_body<F, false>(src, B, H, W, f, Hd, Wd, wide, out, nullptr);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_px_idx_kernel(const PxSrc src, const int* idx, int m, int H, int W, int f, int Hd, int Wd, int wide, float* out) {
+    downscale_px_body<F, true>(src, m, H, W, f, Hd, Wd, wide, out, idx);
+}
+
+// packed 8-bit -> the normalised float32 frame (preprocess_u8 at equal sizes on the repacked frame, bit for bit) and -> uint8 RGB.  One
+// thread per pixel: neighbouring lanes fetch neighbouring pixels and write neighbouring triples; output frame b comes from source frame
+// idx[b] (IDX).
+template <bool IDX>
+HP3D_KERNEL(256)
+void preprocess_px_kernel(const PxSrc P, const int* idx, int B, int H, int W, float* out) {
+    const long total = (long)B * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        long r = i / W;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const Rgb8 q = px_pixel(P, (size_t)(IDX ? idx[b] : b), y, x);
+        float* o = out + (size_t)i * 3;
+        o[0] = u8_norm(q.r); o[1] = u8_norm(q.g); o[2] = u8_norm(q.b);
+    }
+}
+HP3D_KERNEL(256)
+void px_to_rgb_kernel(const PxSrc P, int B, int H, int W, unsigned char* out) {
+    const long total = (long)B * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        long r = i / W;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const Rgb8 q = px_pixel(P, (size_t)b, y, x);
+        unsigned char* o = out + (size_t)i * 3;
+        o[0] = (unsigned char)q.r; o[1] = (unsigned char)q.g; o[2] = (unsigned char)q.b;
+    }
+}
+
 // A detection-frame box (centre_d, crop_size_d) in frame coordinates: centre = centre_d * f + (f - 1) / 2 (the centre of detection pixel
 // p covers frame pixels p f ... p f + f - 1), crop_size = crop_size_d * f, scale from it as mask_grow_epilogue derives it (NumPy's NaN
 // rules: oracle.general.scale_from_crop_size).  Element by element: may run in place.
@@ -1920,6 +2056,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_idx_nv12_kernel(const Nv12Src src, int m, int H, int W, const float* center, const float* scale, const int* idx, int K,
                                      int crop, float* out) {
     crop_and_resize_idx_body(TapNv12{src}, m, H, W, 3, center, scale, idx, K, crop, out);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_idx_px_kernel(const PxSrc src, int m, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                   int crop, float* out) {
+    crop_and_resize_idx_body(TapPx{src}, m, H, W, 3, center, scale, idx, K, crop, out);
 }
 
 // hand_side / centre / scale of the m slots as dense arrays for the lifting stage and kp_detect: latency only
@@ -2449,10 +2590,18 @@ static int downscale_wide(const T* img, int W, int f) {
     const int align = rowb % 16 == 0 ? 16 : rowb % 8 == 0 ? 8 : rowb % 4 == 0 ? 4 : rowb % 2 == 0 ? 2 : 1;
     return ((uintptr_t)img % align == 0 && ((size_t)W * 3 * sizeof(T)) % align == 0) ? 1 : 0;
 }
+// ... a packed surface: the base, the pitch and the stride (0 where one frame is reached) on the alignment of the load
+// that downscale_px_body takes a window row of f pixels with
+static int downscale_wide(const PxSrc& P, int, int f) {
+    const int rowb = f * P.pixel_bytes;
+    const int align = rowb % 16 == 0 ? 16 : rowb % 8 == 0 ? 8 : rowb % 4 == 0 ? 4 : rowb % 2 == 0 ? 2 : 1;
+    return ((uintptr_t)P.px % align == 0 && P.pitch % align == 0 && P.frame_stride % align == 0) ? 1 : 0;
+}
 // One dispatcher for both forms: `lead...` = (B) for the kernels over the whole batch, (idx, m) for the indexed ones -- where the same
 // test holds: a frame is H row pitches long, so every selected frame's base is aligned as the first one's.
-template <typename T, class K0, class K2, class K4, class K8, class... Lead>
-static void downscale_dispatch(K0 k0, K2 k2, K4 k4, K8 k8, const T* img, int frames, int H, int W, int f, float* out, hipStream_t s,
+// (Src = const T* or a PxSrc: whatever downscale_wide takes and the kernels take first)
+template <typename Src, class K0, class K2, class K4, class K8, class... Lead>
+static void downscale_dispatch(K0 k0, K2 k2, K4 k4, K8 k8, const Src img, int frames, int H, int W, int f, float* out, hipStream_t s,
                                Lead... lead) {
     if (frames < 1) return;
     const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
@@ -2529,6 +2678,41 @@ void downscale_nv12_launch(const Nv12Src& src, const int* idx, int frames, int H
         else if (f == 8) HP3D_LAUNCH(downscale_nv12_kernel<8>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, wide, out);
         else HP3D_LAUNCH(downscale_nv12_kernel<0>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, 0, out);
     }
+}
+// ---- packed 8-bit frames ----
+int px_pixel_bytes(int format) { return format < 0 || format > 5 ? 0 : format < 2 ? 3 : 4; }
+PxSrc px_src(const unsigned char* px, int pitch, size_t frame_stride, int format) {
+    // the byte offsets of R, G, B: HP3D_PX_RGB, BGR, RGBA, BGRA, ARGB, ABGR (include/hp3d.h)
+    static const int off[6][3] = {{0, 1, 2}, {2, 1, 0}, {0, 1, 2}, {2, 1, 0}, {1, 2, 3}, {3, 2, 1}};
+    const int* o = off[format >= 0 && format < 6 ? format : 0];
+    const int pb = px_pixel_bytes(format);
+    const int wide = (pb == 4 && (uintptr_t)px % 4 == 0 && pitch % 4 == 0 && frame_stride % 4 == 0) ? 1 : 0;
+    return PxSrc{px, pitch, frame_stride, pb, o[0], o[1], o[2], wide};
+}
+void px_to_rgb_launch(const PxSrc& src, int B, int H, int W, unsigned char* out, hipStream_t s) {
+    HP3D_LAUNCH(px_to_rgb_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, s, src, B, H, W, out);
+}
+void crop_and_resize_px_launch(const PxSrc& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                               int crop, float* out, hipStream_t s) {
+    if (n < 1) return;
+    const dim3 grid(grid_for((long)n * crop * crop)), block(256);
+    if (idx) HP3D_LAUNCH(crop_and_resize_idx_px_kernel, grid, block, 0, s, src, n, H, W, center, scale, idx, K, crop, out);
+    else HP3D_LAUNCH(crop_and_resize_px_kernel, grid, block, 0, s, src, n, H, W, center, scale, crop, out, K);
+}
+void downscale_px_launch(const PxSrc& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s) {
+    if (frames < 1) return;
+    if (f == 1) {
+        const dim3 grid(grid_for((long)frames * H * W)), block(256);
+        if (idx) HP3D_LAUNCH(preprocess_px_kernel<true>, grid, block, 0, s, src, idx, frames, H, W, out);
+        else HP3D_LAUNCH(preprocess_px_kernel<false>, grid, block, 0, s, src, idx, frames, H, W, out);
+        return;
+    }
+    if (idx)
+        downscale_dispatch(downscale_px_idx_kernel<0>, downscale_px_idx_kernel<2>, downscale_px_idx_kernel<4>, downscale_px_idx_kernel<8>, src,
+                           frames, H, W, f, out, s, idx, frames);
+    else
+        downscale_dispatch(downscale_px_kernel<0>, downscale_px_kernel<2>, downscale_px_kernel<4>, downscale_px_kernel<8>, src, frames, H, W,
+                           f, out, s, frames);
 }
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s) {

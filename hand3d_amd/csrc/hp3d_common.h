@@ -556,6 +556,24 @@ void nv12_to_rgb_launch(const Nv12Src& src, int B, int H, int W, unsigned char* 
 void crop_and_resize_nv12_launch(const Nv12Src& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
                                  int crop, float* out, hipStream_t s);
 void downscale_nv12_launch(const Nv12Src& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s);
+// Packed 8-bit frames (the layout and the formats: include/hp3d.h).  PxSrc = frame 0's first byte, the row pitch and the
+// frame stride in bytes (0 where only one frame is reached), the pixel size and the byte offsets of R, G, B in a pixel; passed to the
+// kernels by value.  wide: a pixel may be fetched as ONE aligned 32-bit load (4-byte pixels; base, pitch and stride multiples of 4) --
+// px_src computes it from the addresses.  The launches are the NV12 ones' twins, each bit-equal to its uint8 kernel on the repacked frame.
+struct PxSrc {
+    const unsigned char* px;
+    int pitch;
+    size_t frame_stride;
+    int pixel_bytes, ro, go, bo;
+    int wide;
+    PxSrc at(int b) const { PxSrc o = *this; o.px += (size_t)b * frame_stride; return o; }
+};
+int px_pixel_bytes(int format);                   // 3 or 4; 0: unknown format
+PxSrc px_src(const unsigned char* px, int pitch, size_t frame_stride, int format);
+void px_to_rgb_launch(const PxSrc& src, int B, int H, int W, unsigned char* out, hipStream_t s);
+void crop_and_resize_px_launch(const PxSrc& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                               int crop, float* out, hipStream_t s);
+void downscale_px_launch(const PxSrc& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

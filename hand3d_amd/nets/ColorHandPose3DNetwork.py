@@ -183,7 +183,13 @@ class ColorHandPose3DNetwork(object):
                              % ", ".join(str(getattr(p, 'shape', type(p).__name__)) for p in image))
         return None
 
-    def track(self, image, hand_side, detect_scale=None, partial_detect=None, nv12_matrix=None):
+    def _px_frames(self, image, pixel_format):
+        """The frames of a call with `pixel_format`: never a pair of NV12 planes."""
+        if isinstance(image, tuple) or self._nv12_planes(image) is not None:
+            raise ValueError("pixel_format=%r names a packed frame; image=(y, uv) is a pair of NV12 planes" % (pixel_format,))
+        return image
+
+    def track(self, image, hand_side, detect_scale=None, partial_detect=None, nv12_matrix=None, pixel_format=None):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
             HandSegNet as inference() does; every other call crops with the box the dataset readers' hand_crop rule
@@ -201,13 +207,20 @@ class ColorHandPose3DNetwork(object):
             [B,H/2,W]; a tuple that is no such pair raises ValueError.  The crop
             and the detection frame come straight from the planes; every output equals the call on the uint8 frame
             hand3d_amd.utils.nv12.nv12_to_rgb makes of them, bit for bit.  `nv12_matrix` = 'bt709' | 'bt601' | 'bt709_full' |
-            'bt601_full' sets the engine option of that name, which stays set (None: as it is; a fresh engine has 'bt709'). """
+            'bt601_full' sets the engine option of that name, which stays set (None: as it is; a fresh engine has 'bt709').
+            `pixel_format` = 'rgb' | 'bgr' | 'rgba' | 'bgra' | 'argb' | 'abgr': `image` is uint8 [B,H,W,3 or 4] in that byte order
+             -- what cv2.VideoCapture ('bgr') or a capture surface ('bgra') hands over.  An array whose rows are padded
+            to a pitch, or a region of interest of a wider surface, is read as it lies; the fourth byte is ignored.  Every output
+            equals the call on the uint8 RGB frame hand3d_amd.utils.pixels.to_rgb makes of it, bit for bit.  ValueError: a last axis
+            that does not match the format, frames that are not uint8, an (y, uv) pair.  None: as without the argument. """
         self._detect_scale(detect_scale)
         self._nv12_matrix(nv12_matrix)
         if partial_detect is not None:
             self.engine.set_option('track_partial_detect', '1' if partial_detect else '0')
-        planes = self._nv12_planes(image)
-        if planes is not None:
+        planes = None if pixel_format is not None else self._nv12_planes(image)
+        if pixel_format is not None:
+            o = self.engine.track_step_px(self._px_frames(image, pixel_format), pixel_format, hand_side)
+        elif planes is not None:
             o = self.engine.track_step_nv12(planes[0], planes[1], hand_side)
         else:
             step = self.engine.track_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_step
@@ -219,7 +232,8 @@ class ColorHandPose3DNetwork(object):
         """ The next track() call detects the hand anew (a cut in the video, another hand). """
         self.engine.track_reset()
 
-    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None, nv12_matrix=None, partial_detect=None):
+    def track_hands(self, image, hand_side, max_hands, detect_scale=None, compact=None, nv12_matrix=None, partial_detect=None,
+                    pixel_format=None):
         """ Not in the reference class: track() for up to `max_hands` (1 ... 4) hands per frame.  Slot k of a frame
             keeps following its hand for as long as it is not lost, so the slot index is the hand's identity from frame to frame.
             A call detects (HandSegNet once per frame) after track_hands_reset() or a change of the batch, slot count or frame size,
@@ -231,7 +245,7 @@ class ColorHandPose3DNetwork(object):
             tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track().
             `compact`: as for inference_hands() -- a slot with valid = 0 costs nothing behind its box and returns zeros there and
             confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags.
-            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track().
+            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track().  `pixel_format`: packed 8-bit frames, as for track().
             `partial_detect` = True / False sets the engine option "track_hands_partial_detect", which stays set (None: as it is): a
             step that detects because some frames of the batch lost a hand (or have none to follow) runs HandSegNet on those frames
             only; every slot of the other frames keeps what it has -- a slot without a hand there is filled by the next scheduled
@@ -241,8 +255,10 @@ class ColorHandPose3DNetwork(object):
         self._nv12_matrix(nv12_matrix)
         if partial_detect is not None:
             self.engine.set_option('track_hands_partial_detect', '1' if partial_detect else '0')
-        planes = self._nv12_planes(image)
-        if planes is not None:
+        planes = None if pixel_format is not None else self._nv12_planes(image)
+        if pixel_format is not None:
+            o = self.engine.track_hands_step_px(self._px_frames(image, pixel_format), pixel_format, hand_side, max_hands)
+        elif planes is not None:
             o = self.engine.track_hands_step_nv12(planes[0], planes[1], hand_side, max_hands)
         else:
             step = self.engine.track_hands_step_u8 if np.asarray(image).dtype == np.uint8 else self.engine.track_hands_step

@@ -157,7 +157,7 @@ int hp3d_sync(hp3d_ctx* ctx);
  *                            HandSegNet, the soft-max and the mask growth on the lost frames only, at batch m = their number per chunk; see
  *                            "partial detection" below.  "0": every call enqueues what it did without the option.  Anything else:
  *                            HP3D_ERR_ARG.  hp3d_track_hands_step* and every hp3d_infer_* call IGNORE the option;
- *          "track_hands_partial_detect" = "0" (default) | "1": the same for hp3d_track_hands_step / _dev / _u8 / _nv12 / _nv12_dev: a detect
+ *          "track_hands_partial_detect" = "0" (default) | "1": the same for hp3d_track_hands_step / _dev / _u8 / _nv12[_dev] / _px[_dev]: a detect
  *                            step that flags alone caused runs HandSegNet, the soft-max and the claimed multi-hand growth on the frames that
  *                            have a valid slot lost or no valid slot, at batch m = their number per chunk; see "partial detection, several
  *                            hands" below.  "0": every call enqueues what it did without the option.  Anything else: HP3D_ERR_ARG.
@@ -402,7 +402,7 @@ int hp3d_gather_frames(hp3d_ctx* ctx, const float* image, const uint8_t* image_u
                        float* out);
 
 /* ---- partial detection, several hands (option "track_hands_partial_detect" = "1") ----
- * hp3d_track_hands_step / _dev / _u8 / _nv12 / _nv12_dev only ("tracking several hands per frame" below).  Which steps detect is
+ * hp3d_track_hands_step / _dev / _u8 / _nv12[_dev] / _px[_dev] only ("tracking several hands per frame" below).  Which steps detect is
  * unchanged.  A fresh step runs whole (there is nothing to keep) and so does a scheduled one (option "track_redetect": it is how a hand
  * that enters any picture is found).  Only a detect step that flags alone caused -- a valid slot lost, or an image with no valid slot --
  * can be partial.  Per chunk of nb frames (at most micro_batch / K, as always), with L = the chunk's frames that have a valid slot
@@ -623,6 +623,70 @@ int hp3d_crop_and_resize_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv
                               const float* center, const float* scale, const int32_t* idx, int m, int crop_size, float* out);
 int hp3d_downscale_nv12(hp3d_ctx* ctx, const uint8_t* y, const uint8_t* uv, int B, int H, int W, int pitch, int64_t frame_stride, int f,
                         const int32_t* idx, int m, float* out);
+
+/* ---- packed 8-bit frames: BGR / BGRA / RGBA / ..., any pitch ---------------------
+ * A fourth frame type of the two trackers: what OpenCV (BGR), GPU video post-processors, screen capture and camera SDKs (BGRA / RGBA /
+ * ARGB) deliver, rows padded to a pitch, a region of interest as a view into a wider surface, on the host or -- in place -- on the
+ * device.  Every packed entry point is DEFINED as bit-equal to its uint8 entry point on the frame hp3d_px_to_rgb makes: there are no
+ * new numerics.
+ * Layout.  px points at frame 0.  Row r of frame b starts at px + b frame_stride + r pitch (bytes); pixel c of that row starts
+ *   c pixel_bytes further on.  `format`:                   pixel_bytes   byte offsets of R, G, B                                      */
+#define HP3D_PX_RGB 0  /*                                    3             0, 1, 2                                                     */
+#define HP3D_PX_BGR 1  /*                                    3             2, 1, 0                                                     */
+#define HP3D_PX_RGBA 2 /*                                    4             0, 1, 2   (byte 3 ignored: RGBA and RGBX alike)             */
+#define HP3D_PX_BGRA 3 /*                                    4             2, 1, 0   (byte 3 ignored)                                  */
+#define HP3D_PX_ARGB 4 /*                                    4             1, 2, 3   (byte 0 ignored)                                  */
+#define HP3D_PX_ABGR 5 /*                                    4             3, 2, 1   (byte 0 ignored)                                  */
+/*   The fourth byte is never interpreted -- no premultiplication, no blending -- but it may be read.  H, W >= 16, any parity, within the
+ *   frame-size limit of every frame; pitch >= W pixel_bytes; B = 1 (frame_stride is then ignored) or frame_stride >= pitch (H - 1) +
+ *   W pixel_bytes.  ONLY bytes [r pitch, r pitch + W pixel_bytes) of a row are ever read: the padding may be unmapped, so a 3-byte pixel
+ *   is never fetched with a 4-byte load that reaches past its row.  No alignment is required of px, pitch or frame_stride: alignment
+ *   only selects a faster load (a 4-byte pixel as one 32-bit load where all three are multiples of 4; a detection window's row of
+ *   2 / 4 / 8 pixels in loads of up to 16 bytes where they are multiples of the load), and both paths give the same bits.  A uint8 channel
+ *   becomes a network value as the uint8 path makes it: float(ch) / 255 - 0.5, float32 op by op.
+ * hp3d_track_step_px / hp3d_track_hands_step_px   the surface on the host; the call uploads it at pixel_bytes bytes a pixel (one copy
+ *   where rows and frames are contiguous, packed tight on the way otherwise).  Outputs, state, counters and options as hp3d_track_step_u8 /
+ *   hp3d_track_hands_step_u8 on the repacked frames, bit for bit: "detect_scale", "track_partial_detect", "track_hands_partial_detect",
+ *   "hands_compact", "track_redetect", half-precision trunks and micro-batch chunks included (chunk b0 starts at px + b0 frame_stride).
+ * hp3d_track_step_px_dev / hp3d_track_hands_step_px_dev   px is a device pointer: the caller's surface is read in place, stream-ordered
+ *   like hp3d_track_step_dev; every other pointer is a device pointer too.  (With HP3D_PX_RGB at pitch 3 W this is the device-resident
+ *   form of the uint8 entry points.)
+ * What a step launches on the frame.  A TRACKED step: one crop per chunk, straight from the surface (one fetch per tap; profile row
+ *   "crop_and_resize_px", with "hands_compact" "crop_and_resize_idx_px"; counter "crop_px_launches") and nothing else that reads a frame.
+ *   A DETECT step at "detect_scale" f > 1: the detection frame straight from the surface (exact integer sums; rows "downscale_px" /
+ *   "downscale_px_idx"), then that crop.  A DETECT step at f = 1: the normalised float32 frame with one launch ("preprocess_px"; a partial
+ *   detect step: the frames that detect only, "preprocess_px_idx"), detection and crop from it as the uint8 form does.
+ * Errors, each HP3D_ERR_ARG before any launch or upload with a message that names the argument: an unknown format, px NULL, pitch <
+ *   W pixel_bytes, a frame_stride too short at B > 1, H or W below 16.  Counters and the profile stay untouched.
+ * Out of scope: the single-picture calls (hp3d_infer_full*, hp3d_infer_hands*, hp3d_infer_2d*) get no packed form -- hp3d_px_to_rgb plus
+ *   their _u8 forms serve a one-off picture; resizing on the way in (the frame size is the engine's H x W); planar RGB, 16- and 10-bit
+ *   formats, alpha.
+ * The per-op forms (host pointers; the surface is uploaded as it lies, so the kernels run on the pitch, stride and base misalignment
+ *   -- modulo 16 -- given):
+ * hp3d_px_to_rgb              -> out [B,H,W,3] uint8
+ * hp3d_crop_and_resize_px     as hp3d_crop_and_resize_nv12.  = hp3d_crop_and_resize_u8 / hp3d_crop_and_resize_idx on the repacked frames
+ * hp3d_downscale_px           as hp3d_downscale_nv12 (f = 1: the normalised frame).  = hp3d_downscale_u8 on the repacked frames      */
+int hp3d_track_step_px(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format,
+                       const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                       float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                       int32_t* detected);
+int hp3d_track_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format,
+                           const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                           float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                           int32_t* detected);
+int hp3d_track_hands_step_px(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format, int K,
+                             const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                             float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                             int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_track_hands_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px, int pitch, int64_t frame_stride, int format, int K,
+                                 const float* hand_side, float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap,
+                                 float* keypoint_coord3d, int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost,
+                                 int32_t* detected, int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_px_to_rgb(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, uint8_t* out);
+int hp3d_crop_and_resize_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, int K,
+                            const float* center, const float* scale, const int32_t* idx, int m, int crop_size, float* out);
+int hp3d_downscale_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, int f,
+                      const int32_t* idx, int m, float* out);
 
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65

@@ -8,6 +8,8 @@ hp3d_track_seed in front of every step (always tracked; the seed's two uploads a
 well).
 Also NV12 frames at B = 1, 1080x1920 against the uint8 and float32 forms of the same run: host-frame tracked
 steps, device-frame tracked steps, and the frame-reading rows of a detect step at detect_scale = 4.
+Also packed 8-bit frames (BGRA) in the same run: at B = 1, 1080x1920 the host-frame tracked step against the uint8 and
+NV12 ones and the device-frame tracked step against the NV12 and float32 ones, and the device-frame step at B = 32, 320x320 (key "px").
 Writes one JSON line to profiles/track_bench.json."""
 import argparse
 import ctypes as C
@@ -199,6 +201,83 @@ def nv12_case(e, H, W, steps, warmup):
     return r
 
 
+def px_case(e, B, H, W, steps, warmup, host):
+    """Tracked steps on packed BGRA frames at pitch 4 W against the NV12, uint8 and float32 forms in the same run: device frames, and
+    (host) host frames.  All sides see the same picture: the planes are the synth frames pushed through rgb_to_nv12, the uint8 frame is
+    nv12_to_rgb of them, the BGRA surface is from_rgb of that."""
+    from hand3d_amd.utils.nv12 import nv12_to_rgb, rgb_to_nv12
+    from hand3d_amd.utils.pixels import from_rgb
+    img = synth.make_batch(3, B, H, W)
+    y, uv = rgb_to_nv12(np.clip(np.rint((img + 0.5) * 255.0), 0, 255).astype(np.uint8))
+    u8 = nv12_to_rgb(y, uv)
+    bgra = np.ascontiguousarray(from_rgb(u8, 'bgra', fill=255))
+    f32 = (u8.astype(np.float32) / np.float32(255.0) - np.float32(0.5)).astype(np.float32)
+    hs = synth.hand_sides(B)
+    o = e.infer_full(f32, hs, outputs=('scale', 'center'))
+    kpc, kph, c3 = np.empty((B, 21, 2), np.int32), np.empty((B, 21, 2), np.float64), np.empty((B, 21, 3), np.float32)
+    lost, det, conf = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.float32)
+    p = _lib._ptr
+    tail = lambda: (p(hs), None, None, None, None, p(c3), p(kpc), p(kph), p(conf), p(lost), p(det))
+    seed = lambda: e.track_seed(o['center'], o['scale'], H, W)
+    surf = np.concatenate([y, uv], axis=1)
+    fs_nv = surf.strides[0]
+
+    def host_u8():
+        seed()
+        e._chk(e.lib.hp3d_track_step_u8(e.h, B, H, W, p(u8), H, W, *tail()))
+
+    def host_nv12():
+        seed()
+        e._chk(e.lib.hp3d_track_step_nv12(e.h, B, H, W, p(surf), C.c_void_p(surf.ctypes.data + H * W), W, fs_nv, *tail()))
+
+    def host_px():
+        seed()
+        e._chk(e.lib.hp3d_track_step_px(e.h, B, H, W, p(bgra), 4 * W, 4 * H * W, 3, *tail()))
+    d_f32, d_surf, d_bgra, d_hs = e.to_device(f32), e.to_device(surf), e.to_device(bgra), e.to_device(hs)
+    out = {k: e.dev_alloc(B * n) for k, n in (('coord3d', 63 * 4), ('kp_hw', 42 * 8), ('kp_crop', 42 * 4), ('center', 8), ('scale', 4),
+                                              ('confidence', 4), ('lost', 4), ('detected', 4))}
+    outs = {k: int(v) for k, v in out.items()}
+
+    def dev_f32():
+        seed()
+        e.track_step_dev(B, H, W, d_f32, d_hs, **outs)
+
+    def dev_nv12():
+        seed()
+        e.track_step_nv12_dev(B, H, W, int(d_surf), int(d_surf) + H * W, W, fs_nv, d_hs, **outs)
+
+    def dev_px():
+        seed()
+        e.track_step_px_dev(B, H, W, int(d_bgra), 4 * W, 4 * H * W, 'bgra', d_hs, **outs)
+    calls = {'tracked_f32_dev_ms': dev_f32, 'tracked_nv12_dev_ms': dev_nv12, 'tracked_px_dev_ms': dev_px}
+    if host:
+        calls.update({'tracked_u8_host_ms': host_u8, 'tracked_nv12_host_ms': host_nv12, 'tracked_px_host_ms': host_px})
+    for _ in range(warmup):
+        for fn in calls.values():
+            fn()
+    n0 = e.counter('track_tracked_steps')
+    r = {'B': B, 'H': H, 'W': W, 'format': 'bgra', 'pitch': 4 * W, 'regions': '[min, median, max] ms of three'}
+    r.update({k: spread3(fn, steps, e.sync) for k, fn in calls.items()})
+    assert e.counter('track_tracked_steps') - n0 == 3 * steps * len(calls), "a timed step was not a tracked one"
+    # the crop row of one tracked step of each device form, event-timed: one pass unrecorded, then [min, median, max] of three
+    e.set_profiling(1)
+    rows = {}
+    for k, fn in (('f32', dev_f32), ('nv12', dev_nv12), ('px', dev_px)):
+        ts = []
+        for i in range(4):
+            fn()
+            e.sync()
+            if i:
+                ts.append(sum(ms for name, _, ms, _, _ in e.profile() if name.startswith('crop_and_resize')))
+        rows[k] = [round(t, 4) for t in sorted(ts)]
+    e.set_profiling(0)
+    r['crop_row_dev_ms'] = rows
+    e.track_reset()
+    for b in list(out.values()) + [d_f32, d_surf, d_bgra, d_hs]:
+        b.free()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -212,7 +291,9 @@ def main():
            'cases': [case(e, 1, 240, 320, a.steps, a.warmup), case(e, 1, 1080, 1920, max(a.steps // 2, 5), a.warmup),
                      case(e, 32, 320, 320, max(a.steps // 2, 5), max(a.warmup // 2, 2))],
            'host_u8_1080p': host_u8_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup),
-           'nv12_1080p': nv12_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup)}
+           'nv12_1080p': nv12_case(e, 1080, 1920, max(a.steps // 2, 5), a.warmup),
+           'px': [px_case(e, 1, 1080, 1920, max(a.steps // 2, 5), a.warmup, True),
+                  px_case(e, 32, 320, 320, max(a.steps // 2, 5), max(a.warmup // 2, 2), False)]}
     e.close()
     line = json.dumps(res)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
