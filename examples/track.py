@@ -11,6 +11,8 @@ until a frame reports the hand as lost, which makes the next one detect again.
     python examples/track.py batch.npy --hands 2 --partial-detect   (a lost hand costs its own frame's detection only: DESIGN.md 4.18)
     python examples/track.py video_hd.npy --nv12             (the frames as NV12 planes, what a decoder delivers: DESIGN.md 4.17)
     python examples/track.py video_hd.npy --pixel-format bgra   (the frames as packed BGRA, what a capture surface holds: DESIGN.md 4.19)
+    python examples/track.py video_hd.npy --surfaces bgra,nv12,bgr   (one batch of three streams -- the video at offsets of one frame --
+                                                          each frame a surface of its own in its own format: DESIGN.md 4.20)
 """
 import glob
 import json
@@ -42,6 +44,10 @@ if __name__ == '__main__':
     ap.add_argument('--pixel-format', default=None, metavar='FMT', choices=('rgb', 'bgr', 'rgba', 'bgra', 'argb', 'abgr'),
                     help='re-lay the loaded frames as packed 8-bit pixels in this byte order and track on those: crop and detection '
                          'frame come straight from them (DESIGN.md 4.19); not with --nv12')
+    ap.add_argument('--surfaces', default=None, metavar='FMT0,FMT1,...',
+                    help='track a batch of streams, one per listed format cycled over the batch (rgb ... abgr, nv12): stream k shows the '
+                         'video k frames ahead, and every frame of the batch is a surface of its own in its format (DESIGN.md 4.20); '
+                         'not with --nv12 or --pixel-format')
     ap.add_argument('--min-score', default='off', help='confidence below which a hand counts as lost (calibrate on real weights)')
     ap.add_argument('--float-range', choices=('255', 'normalised'), default='255',
                     help='float frames of a .npy file: 0..255 values (default) or already x/255-0.5')
@@ -50,6 +56,11 @@ if __name__ == '__main__':
         ap.error('give a directory of frames or a .npy file (or --synthetic)')
     if a.nv12 and a.pixel_format:
         ap.error('--nv12 and --pixel-format name two different frame layouts: give one')
+    surf_formats = a.surfaces.split(',') if a.surfaces else []
+    if surf_formats and (a.nv12 or a.pixel_format):
+        ap.error('--surfaces names the layout of every frame of the batch: not with --nv12 or --pixel-format')
+    if any(f not in ('rgb', 'bgr', 'rgba', 'bgra', 'argb', 'abgr', 'nv12') for f in surf_formats):
+        ap.error('--surfaces takes rgb, bgr, rgba, bgra, argb, abgr and nv12, separated by commas')
     from hand3d_amd import synth
     from hand3d_amd.nets.ColorHandPose3DNetwork import ColorHandPose3DNetwork
 
@@ -78,20 +89,32 @@ if __name__ == '__main__':
     hand_side_v = np.array([[1.0, 0.0]], np.float32)                      # run.py:40: left hand
     net.track_reset()
     net.track_hands_reset()
+    nb = max(len(surf_formats), 1)                                       # streams in the batch
+    hand_side_v = np.tile(hand_side_v, (nb, 1))
     if a.hands:
-        hand_side_v = np.tile(hand_side_v, (1, a.hands, 1)).reshape(1, a.hands, 2)          # which slot holds a left hand is the caller's knowledge
-    if a.nv12:
+        hand_side_v = np.tile(hand_side_v, (1, a.hands, 1)).reshape(nb, a.hands, 2)          # which slot holds a left hand is the caller's knowledge
+    if a.nv12 or 'nv12' in surf_formats:
         from hand3d_amd.utils.nv12 import rgb_to_nv12
         net.engine.set_option('nv12_matrix', a.nv12_matrix)
-    if a.pixel_format:
+    if a.pixel_format or surf_formats:
         from hand3d_amd.utils.pixels import from_rgb
-    track_kw = {'pixel_format': a.pixel_format} if a.pixel_format else {}
+    track_kw = {'pixel_format': a.pixel_format} if a.pixel_format else {'pixel_format': surf_formats} if surf_formats else {}
+
+    def as_u8(frame):
+        if frame.dtype != np.uint8:
+            frame = (frame + 0.5) * 255.0 if a.float_range == 'normalised' else frame
+            frame = np.clip(np.floor(np.asarray(frame, np.float64) + 0.5), 0, 255).astype(np.uint8)
+        return frame
+
     for i, frame in enumerate(frames):
         frame = np.asarray(frame)
-        if a.nv12 or a.pixel_format:   # (a video source hands its frames over as they are; here they are made from the loaded frame)
-            if frame.dtype != np.uint8:
-                frame = (frame + 0.5) * 255.0 if a.float_range == 'normalised' else frame
-                frame = np.clip(np.floor(np.asarray(frame, np.float64) + 0.5), 0, 255).astype(np.uint8)
+        if surf_formats:               # stream k: the video k frames ahead, as a surface of its own in format k
+            image_v = []
+            for k, fmt in enumerate(surf_formats):
+                u8 = as_u8(np.asarray(frames[(i + k) % len(frames)]))[None]
+                image_v.append(tuple(p[0] for p in rgb_to_nv12(u8, a.nv12_matrix)) if fmt == 'nv12' else from_rgb(u8, fmt)[0])
+        elif a.nv12 or a.pixel_format:   # (a video source hands its frames over as they are; here they are made from the loaded frame)
+            frame = as_u8(frame)
             image_v = rgb_to_nv12(frame[None], a.nv12_matrix) if a.nv12 else from_rgb(frame[None], a.pixel_format)
         elif frame.dtype == np.uint8:
             image_v = frame[None]                      # tracked steps crop straight from the uint8 frame
@@ -103,14 +126,17 @@ if __name__ == '__main__':
         if a.hands:
             coord3d, kp_hw, _, scale, center, confidence, lost, detected, valid, area = net.track_hands(image_v, hand_side_v, a.hands, compact=a.compact,
                                                                                                **track_kw)
-            print(json.dumps({'frame': i, 'step': 'detect' if net.engine.counter('track_hands_detect_steps') > ndet else 'tracked',
-                              'slots': [{'slot': k, 'valid': int(valid[0, k]), 'detected': int(detected[0, k]), 'area': int(area[0, k]),
-                                         'center': center[0, k].tolist(), 'scale': float(scale[0, k]),
-                                         'confidence': float(confidence[0, k]), 'lost': int(lost[0, k]),
-                                         'wrist_hw': kp_hw[0, k, 0].tolist(), 'wrist_xyz': coord3d[0, k, 0].tolist()}
-                                        for k in range(a.hands)]}))
+            for b in range(nb):
+                print(json.dumps(dict({'frame': i, 'step': 'detect' if net.engine.counter('track_hands_detect_steps') > ndet else 'tracked',
+                                       'slots': [{'slot': k, 'valid': int(valid[b, k]), 'detected': int(detected[b, k]), 'area': int(area[b, k]),
+                                                  'center': center[b, k].tolist(), 'scale': float(scale[b, k]),
+                                                  'confidence': float(confidence[b, k]), 'lost': int(lost[b, k]),
+                                                  'wrist_hw': kp_hw[b, k, 0].tolist(), 'wrist_xyz': coord3d[b, k, 0].tolist()}
+                                                 for k in range(a.hands)]}, **({'stream': b, 'format': surf_formats[b]} if surf_formats else {}))))
             continue
         coord3d, kp_hw, kp_hw_crop, scale, center, confidence, lost, detected = net.track(image_v, hand_side_v, **track_kw)
-        print(json.dumps({'frame': i, 'step': 'detect' if detected[0] else 'tracked', 'center': center[0].tolist(),
-                          'scale': float(scale[0, 0]), 'confidence': float(confidence[0]), 'lost': int(lost[0]),
-                          'wrist_hw': kp_hw[0, 0].tolist(), 'wrist_xyz': coord3d[0, 0].tolist()}))
+        for b in range(nb):
+            print(json.dumps(dict({'frame': i, 'step': 'detect' if detected[b] else 'tracked', 'center': center[b].tolist(),
+                                   'scale': float(scale[b, 0]), 'confidence': float(confidence[b]), 'lost': int(lost[b]),
+                                   'wrist_hw': kp_hw[b, 0].tolist(), 'wrist_xyz': coord3d[b, 0].tolist()},
+                                  **({'stream': b, 'format': surf_formats[b]} if surf_formats else {}))))

@@ -11,7 +11,7 @@ import weakref
 
 import numpy as np
 
-from .utils.pixels import FORMATS
+from .utils.pixels import FORMATS, SURF_NV12
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'libhp3d.so')
@@ -97,6 +97,14 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'hp3d_downscale_px': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                     C.c_int, C.c_void_p]),
+    'hp3d_track_step_surf': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 11),
+    'hp3d_track_step_surf_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 11),
+    'hp3d_track_hands_step_surf': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_track_hands_step_surf_dev': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 14),
+    'hp3d_surf_to_rgb': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'hp3d_crop_and_resize_surf': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_int, C.c_void_p]),
+    'hp3d_downscale_surf': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     'hp3d_track_step_u8': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11),
     'hp3d_track_box': (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
     'hp3d_crop_and_resize_u8': (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -138,6 +146,12 @@ COMM_ID_BYTES = 128
 MAX_HANDS = 4               # HP3D_MAX_HANDS
 TIMING_STAGES = ('HandSegNet', 'mask_crop', 'PoseNet2D', 'lifting', 'total')
 EXPORTS = tuple(sorted(_SIGNATURES))
+
+
+class Surface(C.Structure):
+    """hp3d_surface of include/hp3d.h: one frame of a batch of separate surfaces."""
+    _fields_ = [('data', C.c_void_p), ('chroma', C.c_void_p), ('pitch', C.c_int32), ('format', C.c_int32), ('height', C.c_int32),
+                ('width', C.c_int32)]
 
 _lib = None
 _lib_path = None
@@ -749,6 +763,126 @@ class Engine(object):
         out = np.empty((n, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
         self._chk(self.lib.hp3d_downscale_px(self.h, C.c_void_p(p), B, H, W, pitch, fs, fmt, int(f), _ptr(idx),
                                              0 if idx is None else int(idx.size), _ptr(out)))
+        return out
+
+    # -- a batch of separate surfaces, formats mixed (include/hp3d.h, DESIGN.md 4.20) -------------------
+    @staticmethod
+    def surface_records(records):
+        """[(data address, chroma address or 0, pitch, format, height, width)] -> the hp3d_surface array of the C ABI.  `format` is a
+        name ('rgb' ... 'abgr', 'nv12') or the ABI's number."""
+        arr = (Surface * max(len(records), 1))()
+        for r, (data, chroma, pitch, fmt, height, width) in zip(arr, records):
+            r.data, r.chroma = int(data) or None, int(chroma) or None
+            r.pitch, r.height, r.width = int(pitch), int(height), int(width)
+            r.format = SURF_NV12 if fmt == 'nv12' else FORMATS[fmt][0] if fmt in FORMATS else int(fmt)
+        return arr
+
+    @classmethod
+    def _surfaces(cls, surfaces, formats):
+        """B surfaces and their B format names -> (keepalive, hp3d_surface array, B, H, W).  A packed surface is uint8 [H,W,pixel_bytes],
+        an NV12 one a pair (y [H,W], uv [H/2,W]) of uint8 planes under the name 'nv12'; the pitch comes from the array's strides, so a
+        padded surface or a region of interest of a wider one is passed as it lies (anything else is copied once)."""
+        surfaces, formats = list(surfaces), list(formats)
+        if not surfaces or len(surfaces) != len(formats):
+            raise ValueError("%d surfaces, %d formats: need one format per surface and at least one surface" % (len(surfaces), len(formats)))
+        keep, recs, H, W = [], [], None, None
+        for i, (s, f) in enumerate(zip(surfaces, formats)):
+            if f == 'nv12':
+                if not isinstance(s, (tuple, list)) or len(s) != 2:
+                    raise ValueError("surface %d: format 'nv12' wants a pair (y [H,W], uv [H/2,W]) of uint8 planes" % i)
+                y, uv = np.asarray(s[0]), np.asarray(s[1])
+                if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or uv.shape != (y.shape[0] // 2, y.shape[1]) or y.shape[0] % 2:
+                    raise ValueError("surface %d: format 'nv12' wants a pair (y [H,W], uv [H/2,W]) of uint8 planes" % i)
+                if not (y.strides[1] == 1 and uv.strides == y.strides and y.strides[0] >= y.shape[1]):
+                    surf = np.concatenate([y, uv], axis=0)
+                    y, uv = surf[:y.shape[0]], surf[y.shape[0]:]
+                keep.append((y, uv))
+                recs.append((y.ctypes.data, uv.ctypes.data, y.strides[0], 'nv12') + y.shape)
+            else:
+                if f not in FORMATS:
+                    raise ValueError("surface %d: format must be 'nv12' or one of %s, got %r" % (i, ', '.join(sorted(FORMATS)), f))
+                pb = FORMATS[f][1]
+                if isinstance(s, tuple):
+                    raise ValueError("surface %d: format %r names a packed frame; (y, uv) is a pair of NV12 planes" % (i, f))
+                a = np.asarray(s)
+                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != pb:
+                    raise ValueError("surface %d: format %r wants a uint8 frame [H,W,%d]" % (i, f, pb))
+                if not (a.strides[2] == 1 and a.strides[1] == pb and a.strides[0] >= a.shape[1] * pb):
+                    a = np.ascontiguousarray(a)
+                keep.append(a)
+                recs.append((a.ctypes.data, 0, a.strides[0], f) + a.shape[:2])
+            if H is None:
+                H, W = recs[-1][4:]
+        return keep, cls.surface_records(recs), len(recs), int(H), int(W)
+
+    def track_step_surf(self, surfaces, formats, hand_side, want_kpmap=False):
+        """track_step on B separate surfaces in B formats (_surfaces).  Every output equals track_step_u8 on the stack of the surfaces'
+        RGB frames (utils.pixels.surfaces_to_rgb) bit for bit."""
+        keep, arr, B, H, W = self._surfaces(surfaces, formats)
+        hand_side = _f32(hand_side)
+        assert hand_side.shape == (B, 2), "hand_side must be [B,2]"
+        o = self._track_outputs(B, want_kpmap)
+        self._chk(self.lib.hp3d_track_step_surf(self.h, B, H, W, C.addressof(arr), _ptr(hand_side), *[_ptr(o[k]) for k in self._TRACK_ORDER]))
+        return o
+
+    def track_step_surf_dev(self, B, H, W, records, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0, coord3d=0, kp_crop=0, kp_hw=0,
+                            confidence=0, lost=0, detected=0):
+        """Device-pointer variant (ints).  records: B tuples (data address, chroma address or 0, pitch, format name) of device surfaces,
+        read in place; stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        arr = self.surface_records([tuple(r) + (H, W) for r in records])
+        self._chk(self.lib.hp3d_track_step_surf_dev(self.h, B, H, W, C.addressof(arr), v(hand_side_ptr), v(crop), v(scale), v(center), v(kpmap),
+                                                    v(coord3d), v(kp_crop), v(kp_hw), v(confidence), v(lost), v(detected)))
+
+    def track_hands_step_surf(self, surfaces, formats, hand_side, max_hands, want_kpmap=False):
+        """track_hands_step on B separate surfaces (as track_step_surf); equals track_hands_step_u8 on the stacked RGB frames bit for bit."""
+        keep, arr, B, H, W = self._surfaces(surfaces, formats)
+        hand_side = _f32(hand_side)
+        K = int(max_hands)
+        assert hand_side.shape == (B, K, 2), "hand_side must be [B,max_hands,2]"
+        o = self._track_hands_outputs(B, K, want_kpmap)
+        self._chk(self.lib.hp3d_track_hands_step_surf(self.h, B, H, W, C.addressof(arr), K, _ptr(hand_side),
+                                                      *[_ptr(o[k]) for k in self._TRACK_HANDS_ORDER]))
+        return o
+
+    def track_hands_step_surf_dev(self, B, H, W, K, records, hand_side_ptr, crop=0, scale=0, center=0, kpmap=0, coord3d=0, kp_crop=0, kp_hw=0,
+                                  confidence=0, lost=0, detected=0, valid=0, area=0, claimed=0):
+        """Device-pointer variant (ints; records as for track_step_surf_dev); stream-ordered, call sync() before reading."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        arr = self.surface_records([tuple(r) + (H, W) for r in records])
+        self._chk(self.lib.hp3d_track_hands_step_surf_dev(self.h, B, H, W, C.addressof(arr), int(K), v(hand_side_ptr), v(crop), v(scale),
+                                                          v(center), v(kpmap), v(coord3d), v(kp_crop), v(kp_hw), v(confidence), v(lost),
+                                                          v(detected), v(valid), v(area), v(claimed)))
+
+    def surf_to_rgb(self, surfaces, formats):
+        """B surfaces -> uint8 RGB [B,H,W,3] (= utils.pixels.surfaces_to_rgb under option "nv12_matrix")."""
+        keep, arr, B, H, W = self._surfaces(surfaces, formats)
+        out = np.empty((B, H, W, 3), np.uint8)
+        self._chk(self.lib.hp3d_surf_to_rgb(self.h, C.addressof(arr), B, H, W, _ptr(out)))
+        return out
+
+    def crop_and_resize_surf(self, surfaces, formats, center, scale, K=1, idx=None, crop_size=256):
+        """crop_and_resize straight from B surfaces: center [B*K,2], scale [B*K], K boxes per frame -> [B*K,crop,crop,3]; with idx [m]
+        (slot indices) the crops idx[i] only.  = crop_and_resize_u8 / crop_and_resize_idx on surf_to_rgb."""
+        keep, arr, B, H, W = self._surfaces(surfaces, formats)
+        center, scale = _f32(center).reshape(-1, 2), _f32(scale).reshape(-1)
+        assert center.shape[0] == B * int(K) and scale.shape[0] == B * int(K), "center / scale must hold B*K boxes"
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B * int(K) if idx is None else idx.size
+        out = np.empty((n, crop_size, crop_size, 3), np.float32)
+        self._chk(self.lib.hp3d_crop_and_resize_surf(self.h, C.addressof(arr), B, H, W, int(K), _ptr(center), _ptr(scale), _ptr(idx),
+                                                     0 if idx is None else int(idx.size), int(crop_size), _ptr(out)))
+        return out
+
+    def downscale_surf(self, surfaces, formats, f, idx=None):
+        """The detection frame of B surfaces [B or m,ceil(H/f),ceil(W/f),3] (f = 1: the normalised frame); idx: the frames idx[i] only.
+        = downscale_u8 (f = 1: preprocess_u8 at equal sizes) on surf_to_rgb, bit for bit."""
+        keep, arr, B, H, W = self._surfaces(surfaces, formats)
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        n = B if idx is None else idx.size
+        out = np.empty((n, -(-H // int(f)), -(-W // int(f)), 3), np.float32)
+        self._chk(self.lib.hp3d_downscale_surf(self.h, C.addressof(arr), B, H, W, int(f), _ptr(idx), 0 if idx is None else int(idx.size),
+                                               _ptr(out)))
         return out
 
     def track_box(self, keypoint_hw, H, W, score32=None, margin=None):

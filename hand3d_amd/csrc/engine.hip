@@ -326,6 +326,7 @@ struct Counters {
     long track_hands_partial_frames_run = 0, track_hands_partial_frames_skipped = 0;   // option "track_hands_partial_detect": the same
     long crop_nv12_launches = 0;                    // crops taken straight from an NV12 frame (either crop_and_resize*_nv12_kernel)
     long crop_px_launches = 0;                      // crops taken straight from a packed 8-bit frame (either crop_and_resize*_px_kernel)
+    long crop_surf_launches = 0;                    // crops taken straight from a batch of surfaces (either crop_and_resize*_surf_kernel)
 };
 
 // A page-locked int buffer that small copies fill or drain behind the stream (the trackers' flags, the compaction's maps), the event
@@ -350,6 +351,16 @@ struct CompactBufs {
     HostFlags valid;                    // a chunk's valid flags (detect steps, hp3d_infer_hands*)
     int* d_map = nullptr;
     float *d_hs = nullptr, *d_center = nullptr, *d_scale = nullptr;      // hand_side / centre / scale of the slots that run, dense
+};
+
+// A batch of separate surfaces.  d_rec: the device table, one SurfRec per frame (stream order protects it).  stage: two
+// page-locked buffers of records used in turn; a buffer is rewritten only after the event behind its last upload, so a _dev step never
+// waits for the step in front of it.
+struct SurfTable {
+    int cap = 0;                        // records the buffers hold
+    SurfRec* d_rec = nullptr;
+    HostFlags stage[2];
+    int turn = 0;
 };
 
 // What a context knows about the hands it follows (hp3d_track_*): the boxes for the next step, on the device, and the host's copy of the
@@ -463,6 +474,7 @@ struct hp3d_ctx : Options, Counters {
     TrackState track;
     TrackHandsState track_hands;
     CompactBufs compact;
+    SurfTable surf;
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -1956,19 +1968,139 @@ int upload_px(hp3d_ctx* ctx, int B, int H, int W, const PxArg& a, PxSrc* out) {
     return 0;
 }
 
-// The frames of a chunk of a tracking step: float32, uint8, NV12 or packed 8-bit -- exactly one is set.  The wrappers below switch on the
-// kind, so the branch is written once; the float32 and uint8 launches, profile rows and counters are the ones they were.
+// ---- a batch of separate surfaces, formats mixed (the record: include/hp3d.h) -----------------------------------------
+static_assert(HP3D_SURF_FORMAT_NV12 == HP3D_SURF_NV12, "hp3d_common.h and include/hp3d.h disagree");
+static_assert(sizeof(SurfRec) % sizeof(int) == 0, "the staging buffers count in ints");
+// the bytes of the picture in a row of surface s (0: unknown format)
+static size_t surf_row_bytes(const hp3d_surface& s, int W) {
+    return s.format == HP3D_SURF_NV12 ? (size_t)W : (size_t)W * px_pixel_bytes(s.format);
+}
+// every refusal comes before anything is enqueued and names the surface
+int check_surfaces(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* sf) {
+    if (!sf) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces is NULL");
+    if (B < 1 || H < 16 || W < 16) HP3D_FAIL(ctx, HP3D_ERR_ARG, "bad shape B=%d H=%d W=%d (need B>=1, H,W >=16)", B, H, W);
+    for (int i = 0; i < B; ++i) {
+        const hp3d_surface& s = sf[i];
+        const bool nv = s.format == HP3D_SURF_NV12;
+        if (!nv && !px_pixel_bytes(s.format))
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d].format=%d is none of HP3D_PX_RGB ... HP3D_PX_ABGR (0 ... 5) or HP3D_SURF_NV12 (16)", i,
+                      (int)s.format);
+        if (!s.data) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d].data is NULL", i);
+        if (nv && !s.chroma) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d].chroma is NULL on an NV12 surface", i);
+        if (!nv && s.chroma) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d].chroma must be NULL on a packed format (format=%d)", i, (int)s.format);
+        if (s.height != H || s.width != W)
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d] is %dx%d, the call is %dx%d: mixed sizes are not supported yet", i, (int)s.height,
+                      (int)s.width, H, W);
+        if (nv && ((H | W) & 1))
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d] is NV12: H=%d and W=%d must be even (a chroma sample covers 2 x 2 pixels)", i, H, W);
+        if ((long long)s.pitch < (long long)surf_row_bytes(s, W))
+            HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces[%d].pitch=%d is below the row's %lld bytes", i, (int)s.pitch, (long long)surf_row_bytes(s, W));
+    }
+    return 0;
+}
+int ensure_surf(hp3d_ctx* ctx, int B) {
+    SurfTable& Q = ctx->surf;
+    if (B <= Q.cap) return 0;
+    for (HostFlags& h : Q.stage) CHK(h.wait(ctx));
+    CHK(dev_realloc(ctx, &Q.d_rec, (size_t)B));
+    for (HostFlags& h : Q.stage) CHK(h.resize(ctx, (size_t)B * (sizeof(SurfRec) / sizeof(int)), "surface table"));
+    Q.cap = B;
+    return 0;
+}
+void surf_free(hp3d_ctx* ctx) {
+    SurfTable& Q = ctx->surf;
+    if (Q.d_rec) hipFree(Q.d_rec);
+    for (HostFlags& h : Q.stage) h.free();
+    Q = SurfTable();
+}
+// The table of a call: *h = B records of page-locked staging to fill (surf_rec, from DEVICE addresses), then surf_table_commit copies
+// them to the device table behind the stream.  The staging buffers take turns and each is rewritten only after the event behind its
+// last copy: that copy belongs to the call before the previous one, so the wait holds the host only when it runs two calls ahead of the
+// device -- an event wait, never a stream synchronise.  (A tracker's wait for the previous step's flags orders the copy of every step
+// but the one behind a reset, a failed step or a per-op call; the second buffer makes the rule hold without that case analysis.)
+int surf_table_begin(hp3d_ctx* ctx, int B, SurfRec** h) {
+    CHK(ensure_surf(ctx, B));
+    HostFlags& st = ctx->surf.stage[ctx->surf.turn];
+    CHK(st.wait(ctx));
+    *h = (SurfRec*)st.h;
+    return 0;
+}
+int surf_table_commit(hp3d_ctx* ctx, int B, SurfSrc* out) {
+    SurfTable& Q = ctx->surf;
+    HostFlags& st = Q.stage[Q.turn];
+    Q.turn ^= 1;
+    HIPCHK(ctx, hipMemcpyAsync(Q.d_rec, st.h, sizeof(SurfRec) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
+    CHK(st.record(ctx));
+    *out = surf_src(Q.d_rec, ctx->nv12_matrix);
+    return 0;
+}
+// device surfaces: the records from the caller's addresses, in place
+int surf_table_dev(hp3d_ctx* ctx, int B, const hp3d_surface* sf, SurfSrc* out) {
+    SurfRec* h;
+    CHK(surf_table_begin(ctx, B, &h));
+    for (int b = 0; b < B; ++b) h[b] = surf_rec(sf[b].data, sf[b].chroma, sf[b].pitch, sf[b].format);
+    return surf_table_commit(ctx, B, out);
+}
+// Host surfaces -> d_u8, each packed tight into a slot of its own (4 H W bytes rounded up to 16: a 4-byte surface lands `wide`, and a
+// stream that changes format re-allocates nothing), as upload_px / upload_nv12 pack theirs: one copy where the rows are contiguous, row
+// by row through h_px otherwise.  Only the picture's bytes of a row are read.  The table is built over the upload.
+int upload_surf(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* sf, SurfSrc* out) {
+    const size_t slot = ((size_t)H * W * 4 + 15) / 16 * 16, cap = slot * B, ny = (size_t)H * W;
+    if (cap > ctx->u8_bytes) { CHK(dev_realloc(ctx, &ctx->d_u8, cap)); ctx->u8_bytes = cap; }
+    // (the previous call's upload has completed: every host form ends on a stream synchronise)
+    size_t packed = 0;
+    for (int b = 0; b < B; ++b)
+        if ((size_t)sf[b].pitch != surf_row_bytes(sf[b], W)) packed += sf[b].format == HP3D_SURF_NV12 ? ny + ny / 2 : surf_row_bytes(sf[b], W) * H;
+    ctx->h_px.resize(packed);
+    unsigned char* hp = ctx->h_px.data();
+    SurfRec* h;
+    CHK(surf_table_begin(ctx, B, &h));
+    for (int b = 0; b < B; ++b) {
+        const hp3d_surface& s = sf[b];
+        const size_t row = surf_row_bytes(s, W);
+        unsigned char* d = ctx->d_u8 + b * slot;
+        const bool nv = s.format == HP3D_SURF_NV12;
+        if ((size_t)s.pitch == row) {
+            HIPCHK(ctx, hipMemcpyAsync(d, s.data, row * H, hipMemcpyHostToDevice, ctx->stream));
+            if (nv) HIPCHK(ctx, hipMemcpyAsync(d + ny, s.chroma, ny / 2, hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            const size_t n = nv ? ny + ny / 2 : row * H;
+            for (int r = 0; r < H; ++r) memcpy(hp + (size_t)r * row, s.data + (size_t)r * s.pitch, row);
+            for (int r = 0; nv && r < H / 2; ++r) memcpy(hp + ny + (size_t)r * row, s.chroma + (size_t)r * s.pitch, row);
+            HIPCHK(ctx, hipMemcpyAsync(d, hp, n, hipMemcpyHostToDevice, ctx->stream));
+            hp += n;
+        }
+        h[b] = surf_rec(d, nv ? d + ny : nullptr, (int)row, s.format);
+    }
+    return surf_table_commit(ctx, B, out);
+}
+// mean bytes a pixel of the surfaces (the profile rows' traffic figure)
+static double surf_mean_bpp(int B, const hp3d_surface* sf) {
+    double b = 0;
+    for (int i = 0; i < B; ++i) b += sf[i].format == HP3D_SURF_NV12 ? 1.5 : px_pixel_bytes(sf[i].format);
+    return b / B;
+}
+
+// The frames of a chunk of a tracking step: float32, uint8, NV12, packed 8-bit or separate surfaces -- exactly one is set.  The wrappers
+// below switch on the kind, so the branch is written once; the float32 and uint8 launches, profile rows and counters are the ones they
+// were.
 struct FrameSrc {
     const float* f32 = nullptr;
     const unsigned char* u8 = nullptr;
     const Nv12Src* nv12 = nullptr;
     const PxSrc* px = nullptr;
-    bool raw() const { return u8 || nv12 || px; }
+    const SurfSrc* surf = nullptr;
+    double surf_bpp = 0;                  // surf: mean bytes a pixel of the step's surfaces
+    bool raw() const { return u8 || nv12 || px || surf; }
 };
 // the nb * K crops of nb frames, K boxes per frame, into d_crop
 int crop_frames(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* bc, const float* bs) {
     const int ns = nb * K;
-    if (src.px) {
+    if (src.surf) {
+        ProfScope ps(ctx, "crop_and_resize_surf", "crop_and_resize_surf", 0.0, src.surf_bpp * nb * H * W + 4.0 * ns * 256 * 256 * 3);
+        crop_and_resize_surf_launch(*src.surf, ns, H, W, bc, bs, nullptr, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_surf_launches;
+    } else if (src.px) {
         ProfScope ps(ctx, "crop_and_resize_px", "crop_and_resize_px", 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * ns * 256 * 256 * 3);
         crop_and_resize_px_launch(*src.px, ns, H, W, bc, bs, nullptr, K, 256, ctx->d_crop, ctx->stream);
         ++ctx->crop_px_launches;
@@ -1990,7 +2122,11 @@ int crop_frames(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W,
 // the m crops of the slots idx[i] (option "hands_compact"), dense, into d_crop
 int crop_frames_idx(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, int W, const float* center, const float* scale, const int* d_idx,
                     int m) {
-    if (src.px) {
+    if (src.surf) {
+        ProfScope ps(ctx, "crop_and_resize_idx_surf", "crop_and_resize_idx_surf", 0.0, src.surf_bpp * nb * H * W + 4.0 * m * 256 * 256 * 3);
+        crop_and_resize_surf_launch(*src.surf, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
+        ++ctx->crop_surf_launches;
+    } else if (src.px) {
         ProfScope ps(ctx, "crop_and_resize_idx_px", "crop_and_resize_idx_px", 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * m * 256 * 256 * 3);
         crop_and_resize_px_launch(*src.px, m, H, W, center, scale, d_idx, K, 256, ctx->d_crop, ctx->stream);
         ++ctx->crop_px_launches;
@@ -2011,7 +2147,11 @@ int crop_frames_idx(hp3d_ctx* ctx, const FrameSrc& src, int nb, int K, int H, in
 }
 // a raw frame as the normalised float32 frame in d_image: all nb frames (idx null) or the frames idx[i], i < nb, dense
 int normalise_frames(hp3d_ctx* ctx, const FrameSrc& src, const int* idx, int nb, int H, int W) {
-    if (src.px) {
+    if (src.surf) {
+        const char* row = idx ? "preprocess_surf_idx" : "preprocess_surf";
+        ProfScope ps(ctx, row, row, 0.0, src.surf_bpp * nb * H * W + 4.0 * nb * H * W * 3);
+        downscale_surf_launch(*src.surf, idx, nb, H, W, 1, ctx->d_image, ctx->stream);
+    } else if (src.px) {
         const char* row = idx ? "preprocess_px_idx" : "preprocess_px";
         ProfScope ps(ctx, row, row, 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * nb * H * W * 3);
         downscale_px_launch(*src.px, idx, nb, H, W, 1, ctx->d_image, ctx->stream);
@@ -2038,7 +2178,12 @@ int run_detect_reduced(hp3d_ctx* ctx, const FrameSrc& src, int nb, int H, int W,
     const int f = ctx->detect_scale, slots = nb * std::max(K, 1);
     const float* d_img = src.f32;
     const unsigned char* d_u8 = src.u8;
-    if (src.px) {
+    if (src.surf) {
+        const char* row = idx ? "downscale_surf_idx" : "downscale_surf";
+        ProfScope ps(ctx, row, row, 0.0, src.surf_bpp * nb * H * W + 4.0 * nb * Hd * Wd * 3);
+        downscale_surf_launch(*src.surf, idx, nb, H, W, f, ctx->d_image, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+    } else if (src.px) {
         const char* row = idx ? "downscale_px_idx" : "downscale_px";
         ProfScope ps(ctx, row, row, 0.0, (double)src.px->pixel_bytes * nb * H * W + 4.0 * nb * Hd * Wd * 3);
         downscale_px_launch(*src.px, idx, nb, H, W, f, ctx->d_image, ctx->stream);
@@ -2084,7 +2229,8 @@ struct StepIn {
     const float* hand_side = nullptr;
     bool dev = false;
     const PxArg* px = nullptr;
-    bool raw() const { return image_u8 || nv || px; }    // uint8, NV12 or packed 8-bit frames: no float32 frame comes in
+    const hp3d_surface* surf = nullptr;                  // B records in host memory
+    bool raw() const { return image_u8 || nv || px || surf; }    // uint8, NV12, packed 8-bit frames or surfaces: no float32 frame comes in
 };
 // Where a step's results go, one entry per slot (null: skipped); device pointers when the step's input is.
 struct StepOut {
@@ -2117,8 +2263,10 @@ struct StepFrames {
     const int H, W;
     Nv12Src nvs{}, nvc{};
     PxSrc pxs{}, pxc{};
+    SurfSrc sfs{}, sfc{};                 // the step's table, and it from the chunk's first frame on
+    double surf_bpp = 0;
     const float* d_hs = nullptr;          // the chunk's hand_side on the device
-    FrameSrc src;                         // the chunk's frames (src.nv12 and src.px point into this record)
+    FrameSrc src;                         // the chunk's frames (src.nv12, src.px and src.surf point into this record)
     int upload(hp3d_ctx* ctx, int B) {
         if (in.image_u8) {
             const size_t nbytes = (size_t)B * H * W * 3;
@@ -2129,6 +2277,9 @@ struct StepFrames {
         else if (in.nv) CHK(upload_nv12(ctx, B, H, W, *in.nv, &nvs));
         if (in.px && in.dev) pxs = px_src(in.px->px, in.px->pitch, B > 1 ? (size_t)in.px->frame_stride : 0, in.px->format);
         else if (in.px) CHK(upload_px(ctx, B, H, W, *in.px, &pxs));
+        if (in.surf && in.dev) CHK(surf_table_dev(ctx, B, in.surf, &sfs));
+        else if (in.surf) CHK(upload_surf(ctx, B, H, W, in.surf, &sfs));
+        if (in.surf) surf_bpp = surf_mean_bpp(B, in.surf);
         return 0;
     }
     int chunk(hp3d_ctx* ctx, int b0, int nb, int K, bool stage) {
@@ -2150,6 +2301,9 @@ struct StepFrames {
         src.nv12 = in.nv ? &nvc : nullptr;
         pxc = pxs.at(b0);
         src.px = in.px ? &pxc : nullptr;
+        sfc = sfs.at(b0);
+        src.surf = in.surf ? &sfc : nullptr;
+        src.surf_bpp = surf_bpp;
         return 0;
     }
 };
@@ -2237,6 +2391,7 @@ int track_step_impl(hp3d_ctx* ctx, int B, int H, int W, const StepIn& in, const 
     if ((!in.image && !in.raw()) || !in.hand_side) HP3D_FAIL(ctx, HP3D_ERR_ARG, "image / hand_side is NULL");
     if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
     if (in.px) CHK(check_px(ctx, B, H, W, *in.px));
+    if (in.surf) CHK(check_surfaces(ctx, B, H, W, in.surf));
     CHK(check_img(ctx, B, H, W));
     const bool dev = in.dev;
     int Hd, Wd;
@@ -2587,6 +2742,7 @@ int track_hands_step_impl(hp3d_ctx* ctx, int B, int H, int W, int K, const StepI
     if (K < 1 || K > HP3D_MAX_HANDS) HP3D_FAIL(ctx, HP3D_ERR_ARG, "max hands K=%d must be in 1 ... %d", K, HP3D_MAX_HANDS);
     if (in.nv) CHK(check_nv12(ctx, B, H, W, *in.nv));
     if (in.px) CHK(check_px(ctx, B, H, W, *in.px));
+    if (in.surf) CHK(check_surfaces(ctx, B, H, W, in.surf));
     CHK(check_img(ctx, B, H, W));
     const bool dev = in.dev;
     int Hd, Wd;
@@ -2892,6 +3048,7 @@ int hp3d_destroy(hp3d_ctx* ctx) {
     track_free(ctx);
     track_hands_free(ctx);
     compact_free(ctx);
+    surf_free(ctx);
     if (ctx->d_u8) hipFree(ctx->d_u8);
     if (ctx->blob16) hipFree(ctx->blob16);
     if (ctx->d_concat16) hipFree(ctx->d_concat16);
@@ -3560,6 +3717,27 @@ int hp3d_track_hands_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8
                                          keypoint_hw, confidence, lost, detected, valid, area, claimed});
 }
 
+int hp3d_track_hands_step_surf(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, int K, const float* hand_side,
+                               float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                               int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                               int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!surfaces) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces is NULL");
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, nullptr, hand_side, false, nullptr, surfaces},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
+}
+int hp3d_track_hands_step_surf_dev(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, int K, const float* hand_side,
+                                   float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                                   int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                                   int32_t* valid, int32_t* area, int32_t* claimed) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!surfaces) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces is NULL");
+    return track_hands_step_impl(ctx, B, H, W, K, StepIn{nullptr, nullptr, nullptr, hand_side, true, nullptr, surfaces},
+                                 StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop,
+                                         keypoint_hw, confidence, lost, detected, valid, area, claimed});
+}
+
 int hp3d_track_hands_box(hp3d_ctx* ctx, int B, int K, int H, int W, const double* keypoint_hw, const float* score32, float margin,
                          const int32_t* valid, const float* box_center, const float* box_scale, float* center, float* scale,
                          float* confidence, int32_t* lost) {
@@ -3687,6 +3865,25 @@ int hp3d_track_step_px_dev(hp3d_ctx* ctx, int B, int H, int W, const uint8_t* px
     if (!ctx) return HP3D_ERR_ARG;
     const PxArg pa{px, pitch, (long long)frame_stride, format};
     return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, nullptr, hand_side, true, &pa},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
+}
+
+int hp3d_track_step_surf(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, const float* hand_side, float* image_crop,
+                         float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop,
+                         double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!surfaces) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces is NULL");
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, nullptr, hand_side, false, nullptr, surfaces},
+                           StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
+                                   confidence, lost, detected});
+}
+int hp3d_track_step_surf_dev(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, const float* hand_side, float* image_crop,
+                             float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                             int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected) {
+    if (!ctx) return HP3D_ERR_ARG;
+    if (!surfaces) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf: surfaces is NULL");
+    return track_step_impl(ctx, B, H, W, StepIn{nullptr, nullptr, nullptr, hand_side, true, nullptr, surfaces},
                            StepOut{image_crop, scale_crop, center, keypoints_scoremap, keypoint_coord3d, keypoint_hw_crop, keypoint_hw,
                                    confidence, lost, detected});
 }
@@ -4066,6 +4263,106 @@ int hp3d_downscale_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int
     if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
     float* d_o = S.alloc<float>(no); NN(ctx, d_o);
     downscale_px_launch(src, d_i, n, H, W, f, d_o, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+
+// ---- a batch of separate surfaces: the per-op forms -----------------------------------------------------------------
+// Every host surface -> an allocation of its own on the device (NV12: one per plane), at the caller's pitch and base misalignment
+// (modulo 16), so that the kernels run on what they were given and every surface decides its own wide paths.  Only the picture's bytes
+// of a row are read on the host: the rows are placed into spans of 255s that are then uploaded.
+static int upload_surf_as_is(hp3d_ctx* ctx, Scratch& S, int B, int H, int W, const hp3d_surface* sf, SurfSrc* out) {
+    // plane p of surface b: rows[p] rows of `row` bytes at the surface's pitch
+    auto planes = [&](const hp3d_surface& s, const unsigned char** base, int* rows) {
+        base[0] = s.data; rows[0] = H;
+        base[1] = s.chroma; rows[1] = H / 2;
+        return s.format == HP3D_SURF_NV12 ? 2 : 1;
+    };
+    size_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const unsigned char* base[2]; int rows[2];
+        const int np = planes(sf[b], base, rows);
+        for (int p = 0; p < np; ++p) total += (uintptr_t)base[p] % 16 + (size_t)sf[b].pitch * (rows[p] - 1) + surf_row_bytes(sf[b], W);
+    }
+    std::vector<unsigned char>& h = ctx->h_px;
+    h.assign(total, 255);
+    SurfRec* rec;
+    CHK(surf_table_begin(ctx, B, &rec));
+    size_t at = 0;
+    for (int b = 0; b < B; ++b) {
+        const hp3d_surface& s = sf[b];
+        const size_t row = surf_row_bytes(s, W);
+        const unsigned char* base[2]; int rows[2];
+        const int np = planes(s, base, rows);
+        const unsigned char* d_plane[2] = {nullptr, nullptr};
+        for (int p = 0; p < np; ++p) {
+            const size_t lead = (uintptr_t)base[p] % 16, span = lead + (size_t)s.pitch * (rows[p] - 1) + row;
+            for (int r = 0; r < rows[p]; ++r) memcpy(&h[at + lead + (size_t)r * s.pitch], base[p] + (size_t)r * s.pitch, row);
+            unsigned char* d = S.upload(&h[at], span); NN(ctx, d);
+            d_plane[p] = d + lead;
+            at += span;
+        }
+        rec[b] = surf_rec(d_plane[0], d_plane[1], s.pitch, s.format);
+    }
+    return surf_table_commit(ctx, B, out);
+}
+int hp3d_surf_to_rgb(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, uint8_t* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    CHK(check_surfaces(ctx, B, H, W, surfaces));
+    if (!out) HP3D_FAIL(ctx, HP3D_ERR_ARG, "surf_to_rgb: out is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    SurfSrc src;
+    CHK(upload_surf_as_is(ctx, S, B, H, W, surfaces, &src));
+    const size_t no = (size_t)B * H * W * 3;
+    unsigned char* d_o = S.alloc<unsigned char>(no); NN(ctx, d_o);
+    surf_to_rgb_launch(src, B, H, W, d_o, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no, hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_crop_and_resize_surf(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, int K, const float* center,
+                              const float* scale, const int32_t* idx, int m, int crop_size, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    CHK(check_surfaces(ctx, B, H, W, surfaces));
+    if (!center || !scale || !out || K < 1 || K > HP3D_MAX_HANDS || crop_size < 1) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_surf: bad arguments");
+    if (idx && (m < 0 || m > B * K)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "crop_and_resize_surf: m = %d must be in 0 ... B K = %d", m, B * K);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B * K) HP3D_FAIL(ctx, HP3D_ERR_ARG, "idx[%d] = %d is no slot of %d", i, (int)idx[i], B * K);
+    const int n = idx ? m : B * K;
+    if (n == 0) return 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    SurfSrc src;
+    CHK(upload_surf_as_is(ctx, S, B, H, W, surfaces, &src));
+    const size_t no = (size_t)n * crop_size * crop_size * 3;
+    float* d_c = S.upload(center, (size_t)B * K * 2); NN(ctx, d_c);
+    float* d_s = S.upload(scale, (size_t)B * K); NN(ctx, d_s);
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    crop_and_resize_surf_launch(src, n, H, W, d_c, d_s, d_i, K, crop_size, d_o, ctx->stream);
+    ++ctx->crop_surf_launches;
+    HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_op(ctx);
+}
+int hp3d_downscale_surf(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, int f, const int32_t* idx, int m, float* out) {
+    if (!ctx) return HP3D_ERR_ARG;
+    CHK(check_surfaces(ctx, B, H, W, surfaces));
+    if (!out || f < 1 || f > 8) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_surf: bad arguments (f = %d must be in 1 ... 8)", f);
+    if (idx && (m < 1 || m > B)) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_surf: m = %d must be in 1 ... B = %d", m, B);
+    for (int i = 0; idx && i < m; ++i)
+        if (idx[i] < 0 || idx[i] >= B) HP3D_FAIL(ctx, HP3D_ERR_ARG, "downscale_surf: idx[%d] = %d is no frame of %d", i, (int)idx[i], B);
+    const int n = idx ? m : B;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch S(ctx);
+    SurfSrc src;
+    CHK(upload_surf_as_is(ctx, S, B, H, W, surfaces, &src));
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const size_t no = (size_t)n * Hd * Wd * 3;
+    int32_t* d_i = nullptr;
+    if (idx) { d_i = S.upload(idx, (size_t)m); NN(ctx, d_i); }
+    float* d_o = S.alloc<float>(no); NN(ctx, d_o);
+    downscale_surf_launch(src, d_i, n, H, W, f, d_o, ctx->stream);
     HIPCHK(ctx, hipMemcpyAsync(out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     return finish_op(ctx);
 }
@@ -4579,6 +4876,7 @@ int hp3d_get_counter(hp3d_ctx* ctx, const char* name, long long* value) {
         {"frame_gather_launches", &Counters::frame_gather_launches, false},
         {"crop_nv12_launches", &Counters::crop_nv12_launches, false},
         {"crop_px_launches", &Counters::crop_px_launches, false},
+        {"crop_surf_launches", &Counters::crop_surf_launches, false},
     };
     const std::string k(name);
     for (const auto& c : table)

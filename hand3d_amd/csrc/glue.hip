@@ -335,9 +335,41 @@ struct TapPx {
         v[0] = u8_norm(p.r); v[1] = u8_norm(p.g); v[2] = u8_norm(p.b);
     }
 };
+// ---- a batch of separate surfaces, formats mixed -------------------------------------------------------------------------
+// Frame `fr` is record S.rec[fr]: a packed surface or an NV12 one, at its own address and pitch.  The record is seen through a one-frame
+// PxSrc / Nv12Src view (frame stride 0, frame 0), so the unpack and the colour rule stay written once, in px_pixel and nv12_pixel.
+__device__ __forceinline__ PxSrc surf_px(const SurfRec& R) { return PxSrc{R.data, R.pitch, 0, R.pixel_bytes, R.ro, R.go, R.bo, R.wide}; }
+__device__ __forceinline__ Nv12Src surf_nv12(const SurfSrc& S, const SurfRec& R) {
+    return Nv12Src{R.data, R.chroma, R.pitch, 0, S.ky, S.yoff, S.rv, S.gu, S.gv, S.bu};
+}
+__device__ __forceinline__ Rgb8 surf_pixel(const SurfSrc& S, const SurfRec& R, int r, int c) {
+    return R.nv12 ? nv12_pixel(surf_nv12(S, R), 0, r, c) : px_pixel(surf_px(R), 0, r, c);
+}
+// A surface tap: frame(fr) reads the record ONCE per output pixel into registers; its four taps then cost one fetch each, as TapPx's and
+// TapNv12's do -- no second dependent load per tap.  A 256 x 256 crop is a whole number of workgroups, so the record and the format
+// branch are uniform over a workgroup of the tracking steps' crops.
+struct TapSurfFrame {
+    SurfSrc S;
+    SurfRec R;
+    __device__ __forceinline__ void pixel(size_t, int r, int c, float* v) const {
+        const Rgb8 p = surf_pixel(S, R, r, c);
+        v[0] = u8_norm(p.r); v[1] = u8_norm(p.g); v[2] = u8_norm(p.b);
+    }
+};
+struct TapSurf {
+    SurfSrc S;
+    static constexpr bool PIXEL = true;
+    __device__ __forceinline__ TapSurfFrame frame(size_t fr) const { return TapSurfFrame{S, S.rec[fr]}; }
+    __device__ __forceinline__ void pixel(size_t fr, int r, int c, float* v) const { frame(fr).pixel(0, r, c, v); }
+};
+// what the four taps of one output pixel are read through: the tap itself, or a surface tap bound to its frame's record
+template <class Tap>
+__device__ __forceinline__ const Tap& tap_frame(const Tap& tap, size_t) { return tap; }
+__device__ __forceinline__ TapSurfFrame tap_frame(const TapSurf& tap, size_t fr) { return tap.frame(fr); }
 // the four taps of an output pixel of a PIXEL tap, interpolated as crop_and_resize_body does per channel
 template <class Tap>
-__device__ __forceinline__ void crop_pixel_taps(const Tap& tap, size_t fr, int ty0, int ty1, int tx0, int tx1, float ly, float lx, float* o) {
+__device__ __forceinline__ void crop_pixel_taps(const Tap& tap0, size_t fr, int ty0, int ty1, int tx0, int tx1, float ly, float lx, float* o) {
+    const auto& tap = tap_frame(tap0, fr);
     float tl[3], tr[3], bl[3], br[3];
     tap.pixel(fr, ty0, tx0, tl); tap.pixel(fr, ty0, tx1, tr);
     tap.pixel(fr, ty1, tx0, bl); tap.pixel(fr, ty1, tx1, br);
@@ -410,6 +442,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_px_kernel(const PxSrc src, int B, int H, int W, const float* center, const float* scale, int crop, float* out,
                                int boxes_per_image) {
     crop_and_resize_body(TapPx{src}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_surf_kernel(const SurfSrc src, int B, int H, int W, const float* center, const float* scale, int crop, float* out,
+                                 int boxes_per_image) {
+    crop_and_resize_body(TapSurf{src}, B, H, W, 3, center, scale, crop, out, boxes_per_image);
 }
 
 HP3D_KERNEL(256)
@@ -1771,10 +1808,36 @@ void downscale_u8_idx_kernel(const unsigned char* img, const int* idx, int m, in
 // uint8 frames' -- downscale_u8 on the converted frame bit for bit.  F > 0 (f = 2, 4, 8 with `wide`: both plane bases, the pitch and the
 // frame stride multiples of F): a full window row is ONE F-byte load of Y, and the window's chroma row -- F / 2 pairs, shared by two luma
 // rows (y0 is even) -- ONE F-byte load per two luma rows.  Odd f, ragged windows and unaligned surfaces: pixel by pixel.
+// the three sums of the window rows [y0, y1) x columns [x0, x0 + nx) of frame sb (also the surface kernels' NV12 branch)
+template <int F>
+__device__ __forceinline__ void downscale_nv12_window(const Nv12Src& P, size_t sb, int y0, int y1, int x0, int nx, int wide, unsigned& s0,
+                                                      unsigned& s1, unsigned& s2) {
+    constexpr int NB = F > 0 ? F : 1;
+    if constexpr (F > 0) if (wide && nx == F) {
+        const size_t fb = sb * P.frame_stride;
+        for (int yy = y0; yy < y1; yy += 2) {          // (H and y0 are even: rows come in pairs that share a chroma row)
+            unsigned char uv[NB], ya[NB], yb[NB];
+            __builtin_memcpy(uv, __builtin_assume_aligned(P.uv + fb + (size_t)(yy >> 1) * P.pitch + x0, NB), NB);
+            __builtin_memcpy(ya, __builtin_assume_aligned(P.y + fb + (size_t)yy * P.pitch + x0, NB), NB);
+            __builtin_memcpy(yb, __builtin_assume_aligned(P.y + fb + (size_t)(yy + 1) * P.pitch + x0, NB), NB);
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                const Rgb8 pa = nv12_convert(P, ya[k], uv[k & ~1], uv[k | 1]);
+                const Rgb8 pb = nv12_convert(P, yb[k], uv[k & ~1], uv[k | 1]);
+                s0 += pa.r + pb.r; s1 += pa.g + pb.g; s2 += pa.b + pb.b;
+            }
+        }
+        return;
+    }
+    for (int yy = y0; yy < y1; ++yy)
+        for (int k = 0; k < nx; ++k) {
+            const Rgb8 p = nv12_pixel(P, sb, yy, x0 + k);
+            s0 += p.r; s1 += p.g; s2 += p.b;
+        }
+}
 template <int F, bool IDX>
 __device__ __forceinline__ void downscale_nv12_body(const Nv12Src P, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
                                                     const int* idx) {
-    constexpr int NB = F > 0 ? F : 1;
     const long total = (long)B * Hd * Wd;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % Wd);
@@ -1784,30 +1847,7 @@ __device__ __forceinline__ void downscale_nv12_body(const Nv12Src P, int B, int 
         const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
         const size_t sb = (size_t)(IDX ? idx[b] : b);
         unsigned s0 = 0, s1 = 0, s2 = 0;
-        bool done = false;
-        if constexpr (F > 0) if (wide && nx == F) {
-            done = true;
-            const size_t fb = sb * P.frame_stride;
-            for (int yy = y0; yy < y1; yy += 2) {          // (H and y0 are even: rows come in pairs that share a chroma row)
-                unsigned char uv[NB], ya[NB], yb[NB];
-                __builtin_memcpy(uv, __builtin_assume_aligned(P.uv + fb + (size_t)(yy >> 1) * P.pitch + x0, NB), NB);
-                __builtin_memcpy(ya, __builtin_assume_aligned(P.y + fb + (size_t)yy * P.pitch + x0, NB), NB);
-                __builtin_memcpy(yb, __builtin_assume_aligned(P.y + fb + (size_t)(yy + 1) * P.pitch + x0, NB), NB);
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    const Rgb8 pa = nv12_convert(P, ya[k], uv[k & ~1], uv[k | 1]);
-                    const Rgb8 pb = nv12_convert(P, yb[k], uv[k & ~1], uv[k | 1]);
-                    s0 += pa.r + pb.r; s1 += pa.g + pb.g; s2 += pa.b + pb.b;
-                }
-            }
-        }
-        if (!done) {
-            for (int yy = y0; yy < y1; ++yy)
-                for (int k = 0; k < nx; ++k) {
-                    const Rgb8 p = nv12_pixel(P, sb, yy, x0 + k);
-                    s0 += p.r; s1 += p.g; s2 += p.b;
-                }
-        }
+        downscale_nv12_window<F>(P, sb, y0, y1, x0, nx, wide, s0, s1, s2);
         const float n = (float)((y1 - y0) * nx);
         float* o = out + (size_t)i * 3;
         o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
@@ -1871,12 +1911,48 @@ void nv12_to_rgb_kernel(const Nv12Src P, int B, int H, int W, unsigned char* out
 // load's alignment): a full window row is F pixel_bytes bytes in the fewest loads of at most 16 bytes -- 8 / 16 / 2 x 16 bytes for 4-byte
 // pixels, and for 3-byte pixels downscale_body<unsigned char, F>'s 6 / 12 / 24 bytes at 2 / 4 / 8-byte alignment, the pitch explicit.
 // A full window lies inside its row, so neither reaches past it.  Odd f, ragged windows and unaligned surfaces: pixel by pixel.
-template <int F, bool IDX>
-__device__ __forceinline__ void downscale_px_body(const PxSrc P, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
-                                                  const int* idx) {
+// the three sums of the window rows [y0, y1) x columns [x0, x0 + nx) of frame sb (also the surface kernels' packed branch)
+template <int F>
+__device__ __forceinline__ void downscale_px_window(const PxSrc& P, size_t sb, int y0, int y1, int x0, int nx, int wide, unsigned& s0,
+                                                    unsigned& s1, unsigned& s2) {
     constexpr int NP = F > 0 ? F : 1;
     constexpr int A4 = NP * 4 >= 16 ? 16 : NP * 4;
     constexpr int A3 = (NP * 3) % 8 == 0 ? 8 : (NP * 3) % 4 == 0 ? 4 : (NP * 3) % 2 == 0 ? 2 : 1;
+    if constexpr (F > 0) if (wide && nx == F) {
+        const unsigned char* p = P.px + sb * P.frame_stride + (size_t)y0 * P.pitch + (size_t)x0 * P.pixel_bytes;
+        if (P.pixel_bytes == 4) {
+            for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
+                unsigned v[NP];
+                __builtin_memcpy(v, __builtin_assume_aligned(p, A4), sizeof(v));
+#pragma unroll
+                for (int k = 0; k < NP; ++k) {
+                    const Rgb8 q = px_unpack(P, v[k]);
+                    s0 += q.r; s1 += q.g; s2 += q.b;
+                }
+            }
+        } else {          // (3-byte pixels: the sums per byte position, sorted into R, G, B once at the end)
+            unsigned t0 = 0, t1 = 0, t2 = 0;
+            for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
+                unsigned char v[NP * 3];
+                __builtin_memcpy(v, __builtin_assume_aligned(p, A3), sizeof(v));
+#pragma unroll
+                for (int k = 0; k < NP * 3; k += 3) { t0 += v[k]; t1 += v[k + 1]; t2 += v[k + 2]; }
+            }
+            s0 = P.ro == 0 ? t0 : P.ro == 1 ? t1 : t2;
+            s1 = P.go == 0 ? t0 : P.go == 1 ? t1 : t2;
+            s2 = P.bo == 0 ? t0 : P.bo == 1 ? t1 : t2;
+        }
+        return;
+    }
+    for (int yy = y0; yy < y1; ++yy)
+        for (int k = 0; k < nx; ++k) {
+            const Rgb8 q = px_pixel(P, sb, yy, x0 + k);
+            s0 += q.r; s1 += q.g; s2 += q.b;
+        }
+}
+template <int F, bool IDX>
+__device__ __forceinline__ void downscale_px_body(const PxSrc P, int B, int H, int W, int f, int Hd, int Wd, int wide, float* out,
+                                                  const int* idx) {
     const long total = (long)B * Hd * Wd;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % Wd);
@@ -1886,40 +1962,7 @@ __device__ __forceinline__ void downscale_px_body(const PxSrc P, int B, int H, i
         const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
         const size_t sb = (size_t)(IDX ? idx[b] : b);
         unsigned s0 = 0, s1 = 0, s2 = 0;
-        bool done = false;
-        if constexpr (F > 0) if (wide && nx == F) {
-            done = true;
-            const unsigned char* p = P.px + sb * P.frame_stride + (size_t)y0 * P.pitch + (size_t)x0 * P.pixel_bytes;
-            if (P.pixel_bytes == 4) {
-                for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
-                    unsigned v[NP];
-                    __builtin_memcpy(v, __builtin_assume_aligned(p, A4), sizeof(v));
-#pragma unroll
-                    for (int k = 0; k < NP; ++k) {
-                        const Rgb8 q = px_unpack(P, v[k]);
-                        s0 += q.r; s1 += q.g; s2 += q.b;
-                    }
-                }
-            } else {          // (3-byte pixels: the sums per byte position, sorted into R, G, B once at the end)
-                unsigned t0 = 0, t1 = 0, t2 = 0;
-                for (int yy = y0; yy < y1; ++yy, p += P.pitch) {
-                    unsigned char v[NP * 3];
-                    __builtin_memcpy(v, __builtin_assume_aligned(p, A3), sizeof(v));
-#pragma unroll
-                    for (int k = 0; k < NP * 3; k += 3) { t0 += v[k]; t1 += v[k + 1]; t2 += v[k + 2]; }
-                }
-                s0 = P.ro == 0 ? t0 : P.ro == 1 ? t1 : t2;
-                s1 = P.go == 0 ? t0 : P.go == 1 ? t1 : t2;
-                s2 = P.bo == 0 ? t0 : P.bo == 1 ? t1 : t2;
-            }
-        }
-        if (!done) {
-            for (int yy = y0; yy < y1; ++yy)
-                for (int k = 0; k < nx; ++k) {
-                    const Rgb8 q = px_pixel(P, sb, yy, x0 + k);
-                    s0 += q.r; s1 += q.g; s2 += q.b;
-                }
-        }
+        downscale_px_window<F>(P, sb, y0, y1, x0, nx, wide, s0, s1, s2);
         const float n = (float)((y1 - y0) * nx);
         float* o = out + (size_t)i * 3;
         o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
@@ -1962,6 +2005,70 @@ void px_to_rgb_kernel(const PxSrc P, int B, int H, int W, unsigned char* out) {
         const int y = (int)(r % H);
         const int b = (int)(r / H);
         const Rgb8 q = px_pixel(P, (size_t)b, y, x);
+        unsigned char* o = out + (size_t)i * 3;
+        o[0] = (unsigned char)q.r; o[1] = (unsigned char)q.g; o[2] = (unsigned char)q.b;
+    }
+}
+
+// ---- a batch of separate surfaces: the detection frame, the normalised frame, the uint8 RGB frame ------------------------
+// One thread per output pixel, as the packed kernels: output frame b comes from record b (or idx[b]), read once per output pixel; its
+// window goes through downscale_px_window / downscale_nv12_window on the one-frame view of the record, wide where THAT surface's own
+// address and pitch allow it (SurfRec::dwide, bit F) -- downscale_u8 on the stacked RGB frames bit for bit on either path.  A workgroup
+// may straddle two frames: the record index is per lane.
+template <int F, bool IDX>
+__device__ __forceinline__ void downscale_surf_body(const SurfSrc S, int B, int H, int W, int f, int Hd, int Wd, float* out, const int* idx) {
+    const long total = (long)B * Hd * Wd;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wd);
+        long r = i / Wd;
+        const int y = (int)(r % Hd);
+        const int b = (int)(r / Hd);
+        const int y0 = y * f, y1 = min(y0 + f, H), x0 = x * f, nx = min(x0 + f, W) - x0;
+        const SurfRec R = S.rec[IDX ? idx[b] : b];
+        const int wide = F > 0 ? (R.dwide >> F) & 1 : 0;
+        unsigned s0 = 0, s1 = 0, s2 = 0;
+        if (R.nv12) downscale_nv12_window<F>(surf_nv12(S, R), 0, y0, y1, x0, nx, wide, s0, s1, s2);
+        else downscale_px_window<F>(surf_px(R), 0, y0, y1, x0, nx, wide, s0, s1, s2);
+        const float n = (float)((y1 - y0) * nx);
+        float* o = out + (size_t)i * 3;
+        o[0] = downscale_finish(s0, n); o[1] = downscale_finish(s1, n); o[2] = downscale_finish(s2, n);
+    }
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_surf_kernel(const SurfSrc src, int B, int H, int W, int f, int Hd, int Wd, float* out) {
+    downscale_surf_body<F, false>(src, B, H, W, f, Hd, Wd, out, nullptr);
+}
+template <int F>
+HP3D_KERNEL(256)
+void downscale_surf_idx_kernel(const SurfSrc src, const int* idx, int m, int H, int W, int f, int Hd, int Wd, float* out) {
+    downscale_surf_body<F, true>(src, m, H, W, f, Hd, Wd, out, idx);
+}
+template <bool IDX>
+HP3D_KERNEL(256)
+void preprocess_surf_kernel(const SurfSrc S, const int* idx, int B, int H, int W, float* out) {
+    const long total = (long)B * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        long r = i / W;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const SurfRec R = S.rec[IDX ? idx[b] : b];
+        const Rgb8 q = surf_pixel(S, R, y, x);
+        float* o = out + (size_t)i * 3;
+        o[0] = u8_norm(q.r); o[1] = u8_norm(q.g); o[2] = u8_norm(q.b);
+    }
+}
+HP3D_KERNEL(256)
+void surf_to_rgb_kernel(const SurfSrc S, int B, int H, int W, unsigned char* out) {
+    const long total = (long)B * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        long r = i / W;
+        const int y = (int)(r % H);
+        const int b = (int)(r / H);
+        const SurfRec R = S.rec[b];
+        const Rgb8 q = surf_pixel(S, R, y, x);
         unsigned char* o = out + (size_t)i * 3;
         o[0] = (unsigned char)q.r; o[1] = (unsigned char)q.g; o[2] = (unsigned char)q.b;
     }
@@ -2061,6 +2168,11 @@ HP3D_KERNEL(256)
 void crop_and_resize_idx_px_kernel(const PxSrc src, int m, int H, int W, const float* center, const float* scale, const int* idx, int K,
                                    int crop, float* out) {
     crop_and_resize_idx_body(TapPx{src}, m, H, W, 3, center, scale, idx, K, crop, out);
+}
+HP3D_KERNEL(256)
+void crop_and_resize_idx_surf_kernel(const SurfSrc src, int m, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                     int crop, float* out) {
+    crop_and_resize_idx_body(TapSurf{src}, m, H, W, 3, center, scale, idx, K, crop, out);
 }
 
 // hand_side / centre / scale of the m slots as dense arrays for the lifting stage and kp_detect: latency only
@@ -2713,6 +2825,62 @@ void downscale_px_launch(const PxSrc& src, const int* idx, int frames, int H, in
     else
         downscale_dispatch(downscale_px_kernel<0>, downscale_px_kernel<2>, downscale_px_kernel<4>, downscale_px_kernel<8>, src, frames, H, W,
                            f, out, s, frames);
+}
+// ---- a batch of separate surfaces ----
+// One record from one surface's OWN address and pitch (a device address: the facts are about what the kernels load).  wide: PxSrc::wide;
+// dwide bit f (f = 2, 4, 8): the wide window loads of that f -- downscale_wide's test for a packed surface, both planes and the pitch on
+// an f-byte grid for an NV12 one, each as for a batch of one frame.
+SurfRec surf_rec(const unsigned char* data, const unsigned char* chroma, int pitch, int format) {
+    SurfRec R{};
+    R.data = data; R.chroma = chroma; R.pitch = pitch;
+    if (format == HP3D_SURF_FORMAT_NV12) {
+        R.nv12 = 1;
+        for (int f = 2; f <= 8; f *= 2)
+            if ((uintptr_t)data % f == 0 && (uintptr_t)chroma % f == 0 && pitch % f == 0) R.dwide |= 1 << f;
+        return R;
+    }
+    const PxSrc P = px_src(data, pitch, 0, format);
+    R.chroma = nullptr;
+    R.pixel_bytes = P.pixel_bytes; R.ro = P.ro; R.go = P.go; R.bo = P.bo; R.wide = P.wide;
+    for (int f = 2; f <= 8; f *= 2)
+        if (downscale_wide(P, 0, f)) R.dwide |= 1 << f;
+    return R;
+}
+SurfSrc surf_src(const SurfRec* d_rec, int matrix) {
+    const Nv12Src c = nv12_src(nullptr, nullptr, 0, 0, matrix);
+    return SurfSrc{d_rec, c.ky, c.yoff, c.rv, c.gu, c.gv, c.bu};
+}
+void surf_to_rgb_launch(const SurfSrc& src, int B, int H, int W, unsigned char* out, hipStream_t s) {
+    HP3D_LAUNCH(surf_to_rgb_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, s, src, B, H, W, out);
+}
+void crop_and_resize_surf_launch(const SurfSrc& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                 int crop, float* out, hipStream_t s) {
+    if (n < 1) return;
+    const dim3 grid(grid_for((long)n * crop * crop)), block(256);
+    if (idx) HP3D_LAUNCH(crop_and_resize_idx_surf_kernel, grid, block, 0, s, src, n, H, W, center, scale, idx, K, crop, out);
+    else HP3D_LAUNCH(crop_and_resize_surf_kernel, grid, block, 0, s, src, n, H, W, center, scale, crop, out, K);
+}
+void downscale_surf_launch(const SurfSrc& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s) {
+    if (frames < 1) return;
+    if (f == 1) {
+        const dim3 grid(grid_for((long)frames * H * W)), block(256);
+        if (idx) HP3D_LAUNCH(preprocess_surf_kernel<true>, grid, block, 0, s, src, idx, frames, H, W, out);
+        else HP3D_LAUNCH(preprocess_surf_kernel<false>, grid, block, 0, s, src, idx, frames, H, W, out);
+        return;
+    }
+    const int Hd = (H + f - 1) / f, Wd = (W + f - 1) / f;
+    const dim3 grid(grid_for((long)frames * Hd * Wd)), block(256);
+    if (idx) {
+        if (f == 2) HP3D_LAUNCH(downscale_surf_idx_kernel<2>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, out);
+        else if (f == 4) HP3D_LAUNCH(downscale_surf_idx_kernel<4>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, out);
+        else if (f == 8) HP3D_LAUNCH(downscale_surf_idx_kernel<8>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, out);
+        else HP3D_LAUNCH(downscale_surf_idx_kernel<0>, grid, block, 0, s, src, idx, frames, H, W, f, Hd, Wd, out);
+    } else {
+        if (f == 2) HP3D_LAUNCH(downscale_surf_kernel<2>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, out);
+        else if (f == 4) HP3D_LAUNCH(downscale_surf_kernel<4>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, out);
+        else if (f == 8) HP3D_LAUNCH(downscale_surf_kernel<8>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, out);
+        else HP3D_LAUNCH(downscale_surf_kernel<0>, grid, block, 0, s, src, frames, H, W, f, Hd, Wd, out);
+    }
 }
 void box_to_frame_launch(const float* center_d, const float* crop_size_d, int n, int f, float* center, float* crop_size, float* scale,
                          hipStream_t s) {

@@ -574,6 +574,32 @@ void px_to_rgb_launch(const PxSrc& src, int B, int H, int W, unsigned char* out,
 void crop_and_resize_px_launch(const PxSrc& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
                                int crop, float* out, hipStream_t s);
 void downscale_px_launch(const PxSrc& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s);
+// A batch of separate surfaces, formats mixed (the caller's record: hp3d_surface in include/hp3d.h).  SurfRec = ONE frame
+// on the device: the plane pointers and the pitch; for a packed surface the pixel size and the byte offsets of R, G, B; and the alignment
+// facts of THAT surface's own address and pitch -- wide (PxSrc::wide) and dwide (bit f, f = 2, 4, 8: the detection frame's wide window
+// loads at that f; downscale_wide's test for a packed surface, the f-byte test of both planes for an NV12 one).  surf_rec fills one from
+// the device addresses.  SurfSrc = a device table of records, frame b at rec[b], plus the ONE set of NV12 coefficients of the launch;
+// passed to the kernels by value.  The launches are the packed ones' twins, each bit-equal to its uint8 kernel on the stacked RGB frames.
+#define HP3D_SURF_FORMAT_NV12 16                  // = HP3D_SURF_NV12 (include/hp3d.h)
+struct SurfRec {
+    const unsigned char* data;
+    const unsigned char* chroma;
+    int pitch;
+    int nv12;
+    int pixel_bytes, ro, go, bo;
+    int wide, dwide;
+};
+struct SurfSrc {
+    const SurfRec* rec;
+    int ky, yoff, rv, gu, gv, bu;
+    SurfSrc at(int b) const { SurfSrc o = *this; o.rec += b; return o; }
+};
+SurfRec surf_rec(const unsigned char* data, const unsigned char* chroma, int pitch, int format);
+SurfSrc surf_src(const SurfRec* d_rec, int matrix);
+void surf_to_rgb_launch(const SurfSrc& src, int B, int H, int W, unsigned char* out, hipStream_t s);
+void crop_and_resize_surf_launch(const SurfSrc& src, int n, int H, int W, const float* center, const float* scale, const int* idx, int K,
+                                 int crop, float* out, hipStream_t s);
+void downscale_surf_launch(const SurfSrc& src, const int* idx, int frames, int H, int W, int f, float* out, hipStream_t s);
 void touch_launch(const float* p, size_t nfloats, float* sink, hipStream_t s);
 void cvt_channels_f16_launch(const float* in, int npix, int C, int in_cs, hp3d_f16* out, int out_cs, hipStream_t s);
 void pad_channels_launch(const float* in, int npix, int C, float* out, int out_cs, hipStream_t s);

@@ -189,6 +189,31 @@ class ColorHandPose3DNetwork(object):
             raise ValueError("pixel_format=%r names a packed frame; image=(y, uv) is a pair of NV12 planes" % (pixel_format,))
         return image
 
+    @staticmethod
+    def _surfaces(image, pixel_format):
+        """(surfaces, formats) where `image` is a list of B separate surfaces -- uint8 arrays [H,W,pixel_bytes] and (y, uv) pairs --
+        under `pixel_format`, one name for all of them or a list of B names ('nv12' for a pair); None for every other call."""
+        many = isinstance(pixel_format, (list, tuple))
+        if many and not isinstance(image, list):
+            raise ValueError("pixel_format=%r lists formats; image must then be a list of as many surfaces" % (pixel_format,))
+        if pixel_format is None or not isinstance(image, list) or not image:
+            return None
+        if not many and ColorHandPose3DNetwork._nv12_planes(image) is not None:
+            return None          # (a list of the two planes of one NV12 batch under a packed name: _px_frames refuses it, as it always did)
+        if not all(isinstance(s, tuple) or (isinstance(s, np.ndarray) and s.ndim == 3) for s in image):
+            if many:
+                raise ValueError("image: a surface is a uint8 array [H,W,pixel_bytes] or a pair (y, uv) of NV12 planes")
+            return None          # (a nested list of numbers: one packed frame, as it always was)
+        formats = list(pixel_format) if many else [pixel_format] * len(image)
+        if len(formats) != len(image):
+            raise ValueError("pixel_format names %d formats, image holds %d surfaces" % (len(formats), len(image)))
+        for i, (s, f) in enumerate(zip(image, formats)):
+            if isinstance(s, tuple) and f != 'nv12':
+                raise ValueError("surface %d: pixel_format=%r names a packed frame; (y, uv) is a pair of NV12 planes" % (i, f))
+            if not isinstance(s, tuple) and f == 'nv12':
+                raise ValueError("surface %d: pixel_format='nv12' wants a pair (y, uv) of planes, got an array" % i)
+        return image, formats
+
     def track(self, image, hand_side, detect_scale=None, partial_detect=None, nv12_matrix=None, pixel_format=None):
         """ Not in the reference class: inference_keypoints() for the frames of a video.  The first call (and any
             call after track_reset(), a change of the batch or frame size, or a step that lost a hand) detects the hand with
@@ -212,13 +237,21 @@ class ColorHandPose3DNetwork(object):
              -- what cv2.VideoCapture ('bgr') or a capture surface ('bgra') hands over.  An array whose rows are padded
             to a pitch, or a region of interest of a wider surface, is read as it lies; the fourth byte is ignored.  Every output
             equals the call on the uint8 RGB frame hand3d_amd.utils.pixels.to_rgb makes of it, bit for bit.  ValueError: a last axis
-            that does not match the format, frames that are not uint8, an (y, uv) pair.  None: as without the argument. """
+            that does not match the format, frames that are not uint8, an (y, uv) pair.  None: as without the argument.
+            `image` = a list of B surfaces with `pixel_format` = one name for all of them or a list of B names: frame b
+            of the batch is surface b, an array of its own -- uint8 [H,W,3 or 4] in a packed format, or a pair (y [H,W], uv [H/2,W])
+            under the name 'nv12' -- each at its own pitch, the formats mixed freely: one stream per frame.  Every output equals the
+            call on the stack hand3d_amd.utils.pixels.surfaces_to_rgb makes of them, bit for bit.  ValueError: a wrong number of
+            names, a pair under a packed name, an array under 'nv12'. """
         self._detect_scale(detect_scale)
         self._nv12_matrix(nv12_matrix)
         if partial_detect is not None:
             self.engine.set_option('track_partial_detect', '1' if partial_detect else '0')
+        surfaces = self._surfaces(image, pixel_format)
         planes = None if pixel_format is not None else self._nv12_planes(image)
-        if pixel_format is not None:
+        if surfaces is not None:
+            o = self.engine.track_step_surf(surfaces[0], surfaces[1], hand_side)
+        elif pixel_format is not None:
             o = self.engine.track_step_px(self._px_frames(image, pixel_format), pixel_format, hand_side)
         elif planes is not None:
             o = self.engine.track_step_nv12(planes[0], planes[1], hand_side)
@@ -245,7 +278,8 @@ class ColorHandPose3DNetwork(object):
             tuple: Engine.track_hands_step returns them.  `detect_scale`: as for track().
             `compact`: as for inference_hands() -- a slot with valid = 0 costs nothing behind its box and returns zeros there and
             confidence = 0; tracked steps add no stream synchronise, detect steps wait once per chunk for the valid flags.
-            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track().  `pixel_format`: packed 8-bit frames, as for track().
+            `image` = (y, uv) and `nv12_matrix`: NV12 frames, as for track().  `pixel_format`: packed 8-bit frames, as for track();
+            a list of B surfaces with one name or B names: one surface per frame, formats mixed, as for track().
             `partial_detect` = True / False sets the engine option "track_hands_partial_detect", which stays set (None: as it is): a
             step that detects because some frames of the batch lost a hand (or have none to follow) runs HandSegNet on those frames
             only; every slot of the other frames keeps what it has -- a slot without a hand there is filled by the next scheduled
@@ -255,8 +289,11 @@ class ColorHandPose3DNetwork(object):
         self._nv12_matrix(nv12_matrix)
         if partial_detect is not None:
             self.engine.set_option('track_hands_partial_detect', '1' if partial_detect else '0')
+        surfaces = self._surfaces(image, pixel_format)
         planes = None if pixel_format is not None else self._nv12_planes(image)
-        if pixel_format is not None:
+        if surfaces is not None:
+            o = self.engine.track_hands_step_surf(surfaces[0], surfaces[1], hand_side, max_hands)
+        elif pixel_format is not None:
             o = self.engine.track_hands_step_px(self._px_frames(image, pixel_format), pixel_format, hand_side, max_hands)
         elif planes is not None:
             o = self.engine.track_hands_step_nv12(planes[0], planes[1], hand_side, max_hands)

@@ -13,6 +13,7 @@ FORMATS = {
     'argb': (4, 4, (1, 2, 3)),
     'abgr': (5, 4, (3, 2, 1)),
 }
+SURF_NV12 = 16          # HP3D_SURF_NV12: the `format` of an NV12 surface in a batch of separate surfaces
 
 
 def to_rgb(frames, pixel_format):
@@ -38,3 +39,17 @@ def from_rgb(rgb, pixel_format, pitch=None, fill=0):
     for c in range(3):
         out[..., off[c]] = rgb[..., c]
     return out
+
+
+def surfaces_to_rgb(surfaces, formats, nv12_matrix='bt709'):
+    """B separate surfaces -> the stack of their RGB frames, uint8 [B,H,W,3]: a packed surface uint8
+    [H,W,pixel_bytes] by `to_rgb`, an NV12 one -- a pair (y [H,W], uv [H/2,W]) under the name 'nv12' -- by utils.nv12.nv12_to_rgb."""
+    from .nv12 import nv12_to_rgb
+    assert len(surfaces) == len(formats) and len(surfaces) > 0, "one format per surface"
+    out = []
+    for s, f in zip(surfaces, formats):
+        if f == 'nv12':
+            out.append(nv12_to_rgb(np.asarray(s[0])[None], np.asarray(s[1])[None], matrix=nv12_matrix)[0])
+        else:
+            out.append(to_rgb(np.asarray(s)[None], f)[0])
+    return np.stack(out)

@@ -688,6 +688,58 @@ int hp3d_crop_and_resize_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int 
 int hp3d_downscale_px(hp3d_ctx* ctx, const uint8_t* px, int B, int H, int W, int pitch, int64_t frame_stride, int format, int f,
                       const int32_t* idx, int m, float* out);
 
+/* ---- a batch whose frames are separate surfaces, formats mixed --------------------
+ * A fifth frame type of the two trackers, for a caller that follows one hand (or K) in each of many streams: frame b of the batch is
+ * surface b -- an allocation of its own, anywhere, in any order of addresses, in its own layout (a packed format or NV12) at its own
+ * pitch.  Two records may name the same surface.  No staging copy, no B calls at batch 1.
+ * `surfaces` is ALWAYS an array of B records in host memory; it is read before the call returns and may be reused at once.  The
+ * pointers inside the records are host pointers in the plain forms and device pointers in the _dev forms.                           */
+#define HP3D_SURF_NV12 16          /* beside HP3D_PX_RGB ... HP3D_PX_ABGR (0 ... 5) */
+typedef struct hp3d_surface {
+    const uint8_t* data;    /* packed: byte 0 of pixel (0, 0); NV12: the luma plane                    */
+    const uint8_t* chroma;  /* NV12: the interleaved chroma plane; packed formats: must be NULL        */
+    int32_t pitch;          /* bytes from one row to the next (NV12: of both planes)                   */
+    int32_t format;         /* HP3D_PX_* or HP3D_SURF_NV12                                             */
+    int32_t height, width;  /* the picture; in this version both must equal the call's H and W         */
+} hp3d_surface;
+/* Definition.  Let rgb[b] = hp3d_px_to_rgb of surface b (packed) or hp3d_nv12_to_rgb of it under option "nv12_matrix" (NV12).  Every
+ *   output of every entry point below equals, bit for bit, the output of the matching uint8 entry point on the stack rgb[0 .. B), under
+ *   every option of the trackers ("detect_scale", "track_partial_detect", "track_hands_partial_detect", "hands_compact", "micro_batch",
+ *   "track_redetect", half-precision trunks); state and counters move as the uint8 step's do.  Only the picture's bytes of a row are
+ *   read, the fourth byte of a 4-byte pixel is never interpreted, and no RGB frame is made on a tracked step.  Alignment of a surface's
+ *   address and pitch only selects faster loads FOR THAT SURFACE; both paths give the same bits.
+ * hp3d_track_step_surf / hp3d_track_hands_step_surf   argument lists of the _px forms with (px, pitch, frame_stride, format) replaced
+ *   by `surfaces`.  Host surfaces: each is uploaded tight (one copy where its rows are contiguous, packed row by row otherwise).
+ * hp3d_track_step_surf_dev / hp3d_track_hands_step_surf_dev   the surfaces are read in place, stream-ordered; every other pointer is a
+ *   device pointer too.  The call adds one small host-to-device copy (48 bytes a frame) and no stream synchronise.
+ * Profile rows: the uint8 step's with _surf where _u8 stands ("crop_and_resize_surf", "crop_and_resize_idx_surf", "preprocess_surf[_idx]",
+ *   "downscale_surf[_idx]"); counter "crop_surf_launches": one per chunk of every step that crops from the surfaces.
+ * Errors, each HP3D_ERR_ARG before anything is enqueued, the tracker's state untouched, the message naming the surface index:
+ *   surfaces NULL; data NULL; chroma NULL on NV12 or non-NULL on a packed format; an unknown format; pitch below the row's bytes;
+ *   height / width other than H / W (mixed sizes are not supported yet); an NV12 surface with odd H or W; B < 1 or H, W < 16.
+ * The per-op forms (host pointers; each surface is uploaded as it lies, at its pitch and base misalignment modulo 16):
+ * hp3d_surf_to_rgb            -> out [B,H,W,3] uint8: the stack rgb[0 .. B)
+ * hp3d_crop_and_resize_surf   as hp3d_crop_and_resize_px.  = hp3d_crop_and_resize_u8 / hp3d_crop_and_resize_idx on the stack
+ * hp3d_downscale_surf         as hp3d_downscale_px (f in 1 ... 8; f = 1: the normalised frame).  = hp3d_downscale_u8 on the stack    */
+int hp3d_track_step_surf(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, const float* hand_side, float* image_crop,
+                         float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d, int32_t* keypoint_hw_crop,
+                         double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected);
+int hp3d_track_step_surf_dev(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, const float* hand_side, float* image_crop,
+                             float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                             int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected);
+int hp3d_track_hands_step_surf(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, int K, const float* hand_side,
+                               float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                               int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                               int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_track_hands_step_surf_dev(hp3d_ctx* ctx, int B, int H, int W, const hp3d_surface* surfaces, int K, const float* hand_side,
+                                   float* image_crop, float* scale_crop, float* center, float* keypoints_scoremap, float* keypoint_coord3d,
+                                   int32_t* keypoint_hw_crop, double* keypoint_hw, float* confidence, int32_t* lost, int32_t* detected,
+                                   int32_t* valid, int32_t* area, int32_t* claimed);
+int hp3d_surf_to_rgb(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, uint8_t* out);
+int hp3d_crop_and_resize_surf(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, int K, const float* center,
+                              const float* scale, const int32_t* idx, int m, int crop_size, float* out);
+int hp3d_downscale_surf(hp3d_ctx* ctx, const hp3d_surface* surfaces, int B, int H, int W, int f, const int32_t* idx, int m, float* out);
+
 /* ---- per-op entry points (unit/parity tests; same kernels the pipeline runs) --------------
  * hp3d_conv2d          NetworkOps.conv/conv_relu (+ max_pool when pool=1): utils/general.py:36-65
  *                      x [B,H,W,Cin], w HWIO, SAME padding incl. the asymmetric stride-2 case.
